@@ -5,6 +5,13 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1
 it is launched by torchrun, one rank per GPU over RCCL.  W untimed warm-up
 steps, then EXACTLY K timed optimizer steps bracketed by barrier +
 device synchronize, wall time MAX over ranks; rank 0 prints ONE JSON line.
+Such a plain run does nothing else.  ``--full`` adds, after the headline and in
+the same line, everything else the benchmark measures: the box calibration
+(fixed GEMM + copy), an AMD SMI sample right after the timed steps and the
+BASELINE configs 2 / 3 / 4 below.  ``--dump-outputs DIR`` writes what the last
+timed step computed (``loss.npy``, ``trained_params.npy``; float32) so that two
+builds can be compared output for output: model, data and sample are seeded,
+so the inputs are identical from run to run.
 
 Workload (BASELINE.json metric/config): Llama-3.1-70B architecture (80 layers,
 h 8192, 64/8 heads, ffn 28672, vocab 128256), random-init bf16 weights
@@ -21,8 +28,8 @@ of the adapter gradients, grad-norm clip and fused AdamW.
 (bf16 params/grads, fp32 master + Adam moments) — BASELINE config 2/3.
 
 BASELINE config 4 (Llama-3.1-70B FULL-parameter fine-tune, sharded over 8
-GPUs): ``--finetune full --parallel zero3 --act-ckpt``.  When the headline run
-is on 8 GPUs (``--config4 auto``) it is ALSO measured after the headline steps,
+GPUs): ``--finetune full --parallel zero3 --act-ckpt``.  When a ``--full`` headline
+run is on 8 GPUs (``--config4 auto``) it is ALSO measured after the headline steps,
 in a fresh 8-rank child job, and reported under ``config4_full_zero3`` in the
 same JSON line.  ``--emulate-world N`` runs ZeRO-3 in one process with world-N
 shard sizes (per-rank memory/compute proxy without link traffic).
@@ -75,12 +82,22 @@ def parse(argv=None):
     ap.add_argument("--device", default=None, help="force 'cpu' for a plumbing run")
     ap.add_argument("--layers", type=int, default=None, help="override n_layers (NOT valid for the headline)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else this benchmark reports: the box "
+                         "calibration, the AMD SMI sample after the timed steps and the BASELINE configs 2 / 3 / 4 "
+                         "whose switch is 'auto'.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line (a phase switched 'on' explicitly still runs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32): "
+                         "loss.npy (the step's mean loss) and trained_params.npy (the fp32 master copy of the "
+                         "trainable parameters after the step's update; a fixed seeded sample when larger than "
+                         f"{DUMP_SAMPLE_ELEMS} elements)")
     ap.add_argument("--no-gemm-table", action="store_true", help="ignore the tuned hipBLASLt solution table")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="zero3 only: one process holding world-N shard sizes (gathers tile the local shard)")
     ap.add_argument("--config4", choices=["auto", "on", "off"], default="auto",
                     help="also measure BASELINE config 4 (70B full fine-tune, ZeRO-3) after the headline; "
-                         "auto = when the headline runs on 8 GPUs")
+                         "auto = with --full when the headline runs on 8 GPUs")
     ap.add_argument("--config4-micro-batch", type=int, default=4)
     # selective checkpointing of the first N of 80 layers (the rest keep their activations).  Emulated
     # world-8 per-rank step, one box (archive/profiles/r4g/c4_ck*.json): N = 56 3,298 ms / 223.5 GB reserved;
@@ -95,10 +112,10 @@ def parse(argv=None):
                     help="hard limit for the config-4 child job; the headline line is printed either way")
     ap.add_argument("--config2", choices=["auto", "on", "off"], default="auto",
                     help="also measure BASELINE config 2 (Llama-3.1-8B FULL fine-tune, DDP) in-process after "
-                         "the headline; auto = when the headline runs on 1 GPU")
+                         "the headline; auto = with --full when the headline runs on 1 GPU")
     ap.add_argument("--config3", choices=["auto", "on", "off"], default="auto",
                     help="also measure BASELINE config 3 (Llama-3.1-8B FULL fine-tune, DDP over all N GPUs) "
-                         "in-process after the headline; auto = when the headline runs on 8 GPUs")
+                         "in-process after the headline; auto = with --full when the headline runs on 8 GPUs")
     ap.add_argument("--config3-zero1", choices=["auto", "on", "off"], default="auto",
                     help="with config 3: ALSO measure it with the optimizer sharded (ZeRO-1: reduce-scatter, "
                          "AdamW on 1/N of the state, all-gather), after config 4 and only if the time budget "
@@ -112,7 +129,8 @@ def parse(argv=None):
     ap.add_argument("--config2-mb4", choices=["auto", "on", "off"], default="auto",
                     help="with config 2: also measure it at micro-batch 4 (the reference's batch of 4)")
     ap.add_argument("--no-calibrate", dest="calibrate", action="store_false",
-                    help="skip the box calibration (8192^3 bf16 GEMM TF/s, 4 GiB copy TB/s) after the timed steps")
+                    help="with --full: skip the box calibration (8192^3 bf16 GEMM TF/s, 4 GiB copy TB/s) after the timed "
+                         "steps")
     ap.add_argument("--full-model", default="llama3.1-8b", help=argparse.SUPPRESS)  # tests: tiny models
     ap.add_argument("--full-steps", type=int, default=10)
     ap.add_argument("--full-warmup", type=int, default=3)
@@ -140,6 +158,7 @@ def _free_port() -> int:
 _T0 = time.time()  # process start: the --time-budget-s clock
 EMIT_MARGIN_S = 30.0  # kept back from every child job: killing a hung one (<= 20 s), the emit, the exit
 _STATE = {"out": None, "emitted": False, "json_out": None, "child": None}
+DUMP_SAMPLE_ELEMS = 8 << 20  # --dump-outputs: at most this many fp32 elements (32 MiB) of the trained parameters
 
 
 def remaining_s(a) -> float:
@@ -255,9 +274,10 @@ def main(argv=None):
         _arm_emit_on_signal(out, a.json_out)
     cuda = env.device.type == "cuda"
     headline = a.model == "llama3.1-70b" and a.finetune == "lora" and a.parallel == "ddp" and not a.layers
-    c2 = a.config2 == "on" or (a.config2 == "auto" and env.world_size == 1 and headline and cuda)
-    c3 = a.config3 == "on" or (a.config3 == "auto" and env.world_size == 8 and headline and cuda)
-    c4 = a.config4 == "on" or (a.config4 == "auto" and env.world_size == 8 and headline and cuda)
+    # everything after the headline is --full's: 'auto' means "with --full, where it applies"
+    c2 = a.config2 == "on" or (a.config2 == "auto" and a.full and env.world_size == 1 and headline and cuda)
+    c3 = a.config3 == "on" or (a.config3 == "auto" and a.full and env.world_size == 8 and headline and cuda)
+    c4 = a.config4 == "on" or (a.config4 == "auto" and a.full and env.world_size == 8 and headline and cuda)
     children = []
     if c3 and env.world_size > 1:
         children.append(("config3", f"config3_8b_full_dp{env.world_size}"))
@@ -270,7 +290,7 @@ def main(argv=None):
         # the same DDP fine-tune over mxllm's own peer-memory collectives: last of all
         children.append(("config3p", f"config3_8b_full_dp{env.world_size}_peer"))
     try:
-        if cuda and a.calibrate:
+        if cuda and a.calibrate and a.full:
             # box speed next to the number: fixed GEMM + copy after the timed steps
             from mxllm.utils.calibrate import calibrate
 
@@ -410,6 +430,7 @@ def run_full(a, env, micro_batch: int | None = None) -> dict:
     b.steps, b.warmup, b.layers = a.full_steps, a.full_warmup, None
     b.act_ckpt, b.act_ckpt_layers, b.sp, b.cp, b.emulate_world = False, None, 1, 1, 0
     b.grad_accum = 1
+    b.dump_outputs = None  # the dump is the headline's
     if micro_batch is not None:
         b.micro_batch = micro_batch
     try:
@@ -471,7 +492,7 @@ def _run_child(a, world: int, argv: list[str], timeout_s: float, tag: str = "", 
     os.close(fd)
     argv = ["--gpus", str(world)] + argv + ["--config2", "off", "--config3", "off", "--config4", "off",
                                             "--no-calibrate", "--json-out", path] + (
-        ["--device", a.device] if a.device else [])
+        ["--device", a.device] if a.device else []) + (["--full"] if a.full else [])  # --full: its AMD SMI sample
     keep = {k: v for k, v in os.environ.items()
             if not (k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                           "ROLE_WORLD_SIZE", "ROLE_NAME", "GROUP_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
@@ -648,6 +669,29 @@ def _gemm_desc(tuned: bool) -> str:
     return f"{lib} + gemm8 (hand-written MFMA HIP kernel) on the {len(gemm._table())} measured-win shapes"
 
 
+def dump_outputs(path: str, loss: torch.Tensor, trainer) -> None:
+    """``--dump-outputs``: what a caller of the timed path holds after its last step, as float32
+    ``.npy`` files under ``path``: the loss ``train_step`` returned, and the trainable parameters
+    it updated (fp32 master, flat layout; this rank's shard under ZeRO).  More than
+    DUMP_SAMPLE_ELEMS parameters are sampled at fixed, seeded positions (sorted, with
+    repetition), so two runs with the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    if hasattr(trainer, "master_fp32"):
+        w = trainer.master_fp32()
+    else:  # ZeRO-3: the rank's shard of the master weights
+        trainer.params_ready()
+        w = trainer.master.float()
+    w = w.detach().reshape(-1)
+    if w.numel() > DUMP_SAMPLE_ELEMS:
+        g = torch.Generator().manual_seed(20240229)
+        idx = torch.randint(0, w.numel(), (DUMP_SAMPLE_ELEMS,), generator=g).sort().values
+        w = w[idx.to(w.device)]
+    np.save(os.path.join(path, "trained_params.npy"), w.float().cpu().numpy())
+
+
 def run(a, env) -> dict:
     """Build the trainer, run W warm-up + K timed steps, return the JSON dict."""
     from mxllm.models import Llama, get_config
@@ -745,12 +789,14 @@ def run(a, env) -> dict:
     sync()
     elapsed = time.perf_counter() - t_start
     gpu_sample = {}
-    if dev.type == "cuda" and os.environ.get("MXLLM_BENCH_SMI", "1") != "0":
+    if a.full and dev.type == "cuda" and os.environ.get("MXLLM_BENCH_SMI", "1") != "0":
         from mxllm.utils.gpumon import sample_device
 
         gpu_sample = sample_device(dev.index)  # clocks / power right after the timed steps
     elapsed = runtime.all_reduce_scalars([elapsed], op="max")[0]
     loss_v = float(loss.float().item()) if loss is not None else float("nan")
+    if a.dump_outputs and env.is_main and loss is not None:
+        dump_outputs(a.dump_outputs, loss, trainer)
     world = emulated or env.world_size  # emulation: tokens of ONE rank of that world
     sq = max(a.sp, a.cp)
     tokens_per_step = a.micro_batch * a.seq_len * a.grad_accum * env.world_size // sq

@@ -10,7 +10,7 @@ cp gpurun_out/bench_rehearsal_w*.json $OUT/ 2>/dev/null
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { echo "smoke rc=$?"; tail -5 $OUT/smoke.txt; exit 1; }
 tail -2 $OUT/smoke.txt
 for i in ${BENCH_RUNS:-1 2}; do
-  timeout -k 10 560 python bench.py > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { echo "bench rc=$?"; tail -5 $OUT/bench_$i.err; exit 1; }
+  timeout -k 10 560 python bench.py --full > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { echo "bench rc=$?"; tail -5 $OUT/bench_$i.err; exit 1; }
   echo "bench $i: $(python -c "import json;j=json.load(open('$OUT/bench_$i.json'));print(j['value'],j['ms_per_step'],j['config2_8b_full']['value'],j['config2_8b_full']['ms_per_step'],j['config2_8b_full_mb4']['value'],j['calibration'])")"
 done
 C4="--model llama3.1-70b --finetune full --parallel zero3 --act-ckpt --act-ckpt-layers 0 --micro-batch 4 --emulate-world 8 --steps 3 --warmup 2 --no-calibrate"

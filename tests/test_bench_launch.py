@@ -5,7 +5,8 @@
 * under torchrun, WORLD_SIZE != --gpus exits 1 before touching any device;
 * the config-4 phase (ZeRO-3 full fine-tune in a fresh child job) is reported
   inside the SAME JSON line;
-* the ZeRO-3 world-N emulation proxy is labelled as such.
+* the ZeRO-3 world-N emulation proxy is labelled as such;
+* everything after the headline is ``--full``'s; ``--dump-outputs`` writes the last step's results.
 Reference launch contract: /root/reference/scripts/run_node0.sh:10-16.
 """
 import json
@@ -49,7 +50,7 @@ def test_world_size_mismatch_exits_1():
 
 
 def test_config4_phase_in_same_line():
-    r = _bench("--gpus", "2", "--config4", "on", "--config4-model", "tiny", "--config4-steps", "1",
+    r = _bench("--gpus", "2", "--full", "--config4", "on", "--config4-model", "tiny", "--config4-steps", "1",
                "--config4-warmup", "1")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -65,8 +66,8 @@ def test_config4_phase_in_same_line():
 def test_config3_zero1_variant_in_same_line():
     """Config 3 runs as plain DDP and, after it, as the same step with the optimizer sharded
     (ZeRO-1); both child results land in the one line."""
-    r = _bench("--gpus", "2", "--config3", "on", "--config3-zero1", "on", "--full-model", "tiny", "--full-steps", "1",
-               "--full-warmup", "1", "--config4", "off")
+    r = _bench("--gpus", "2", "--full", "--config3", "on", "--config3-zero1", "on", "--full-model", "tiny",
+               "--full-steps", "1", "--full-warmup", "1", "--config4", "off")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -94,8 +95,8 @@ def test_world8_rehearsal_with_config3_and_config4():
     import time
 
     t0 = time.time()
-    r = _bench("--gpus", "8", "--config3", "on", "--full-model", "tiny", "--full-steps", "1", "--full-warmup", "1",
-               "--config4", "on", "--config4-model", "tiny", "--config4-steps", "1", "--config4-warmup", "1",
+    r = _bench("--gpus", "8", "--full", "--config3", "on", "--full-model", "tiny", "--full-steps", "1", "--full-warmup",
+               "1", "--config4", "on", "--config4-model", "tiny", "--config4-steps", "1", "--config4-warmup", "1",
                timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     assert time.time() - t0 < 180
@@ -209,7 +210,7 @@ def test_world8_hung_config4_child_keeps_headline_inside_budget():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     t0 = time.time()
-    r = _bench("--gpus", "8", "--config3", "off", "--config4", "on", "--config4-model", "tiny",
+    r = _bench("--gpus", "8", "--full", "--config3", "off", "--config4", "on", "--config4-model", "tiny",
                "--config4-steps", "1", "--config4-warmup", "1", "--time-budget-s", str(budget),
                "--child-min-s", "20", env=env, timeout=300)
     wall = time.time() - t0
@@ -226,7 +227,7 @@ def test_world8_hung_config4_child_keeps_headline_inside_budget():
 
 def test_child_phases_skipped_when_budget_is_spent():
     """With no budget left after the headline, the child phases are not started at all."""
-    r = _bench("--gpus", "2", "--config4", "on", "--config4-model", "tiny", "--time-budget-s", "1",
+    r = _bench("--gpus", "2", "--full", "--config4", "on", "--config4-model", "tiny", "--time-budget-s", "1",
                "--child-min-s", "5")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -247,7 +248,7 @@ def test_sigterm_during_child_phase_prints_headline():
         env.pop(k, None)
     # world 1 (no torchrun parent): the bench process itself runs the headline, then the child
     p = subprocess.Popen([sys.executable, "bench.py", "--device", "cpu", "--model", "tiny", "--steps", "2",
-                          "--warmup", "1", "--seq-len", "64", "--gpus", "1", "--config4", "on",
+                          "--warmup", "1", "--seq-len", "64", "--gpus", "1", "--full", "--config4", "on",
                           "--config4-model", "tiny", "--child-min-s", "5"],
                          cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     try:
@@ -275,3 +276,75 @@ def test_sigterm_during_child_phase_prints_headline():
     assert j["value"] > 0 and "interrupted" in j and j["config4_full_zero3"] == {"skipped": "not reached"}
     _, alive = psutil.wait_procs(kids, timeout=30)
     assert not alive, [k.pid for k in alive]
+
+
+def test_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the last step's loss and the parameters it trained as
+    float32 ``.npy``; the same arguments give the same inputs, so (on the CPU, where the step is
+    deterministic) the same files."""
+    import numpy as np
+
+    got = []
+    for d in ("a", "b"):
+        r = _bench("--gpus", "1", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1 and lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["loss.npy", "trained_params.npy"]
+        loss, w = np.load(tmp_path / d / "loss.npy"), np.load(tmp_path / d / "trained_params.npy")
+        assert loss.dtype == np.float32 and w.dtype == np.float32
+        assert abs(float(loss[0]) - lines[0]["final_loss"]) < 1e-3
+        assert w.size >= lines[0]["trainable_params"] and np.isfinite(w).all()
+        got.append((loss, w))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
+def test_dump_outputs_samples_large_parameter_sets(tmp_path, monkeypatch):
+    """More than DUMP_SAMPLE_ELEMS trained parameters are written as a fixed seeded sample."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 1000)
+    w = torch.arange(50_000, dtype=torch.float32)
+    tr = types.SimpleNamespace(master_fp32=lambda: w)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), tr)
+    a, b = (np.load(tmp_path / d / "trained_params.npy") for d in ("a", "b"))
+    assert a.shape == (1000,) and np.array_equal(a, b) and np.all(np.diff(a) >= 0) and a.max() > 25_000
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch, capsys):
+    """Without ``--full`` a 1-GPU headline run calibrates nothing and measures no other BASELINE
+    configuration; with it, the calibration and both config-2 runs are in the line as before."""
+    import types
+
+    import torch
+
+    import bench
+    from mxllm.parallel import runtime
+    from mxllm.utils import calibrate
+
+    env = types.SimpleNamespace(device=torch.device("cuda", 0), world_size=1, is_main=True, rank=0)
+    monkeypatch.setattr(runtime, "init", lambda: env)
+    monkeypatch.setattr(runtime, "cleanup", lambda: None)
+    monkeypatch.setattr(bench, "run", lambda a, e: {"value": 1.0, "full": a.full})
+    monkeypatch.setattr(bench, "run_full", lambda a, e, micro_batch=None: {"value": 2.0, "mb": micro_batch})
+    monkeypatch.setattr(bench, "_free_gpu_memory", lambda e: None)
+    monkeypatch.setattr(bench, "_arm_emit_on_signal",
+                        lambda out, json_out: bench._STATE.update(out=out, json_out=json_out, emitted=False))
+    monkeypatch.setattr(bench, "_STDOUT", sys.stdout)
+    monkeypatch.setattr(calibrate, "calibrate", lambda d: {"gemm_8192_bf16_tflops": 1.0})
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setenv("MXLLM_XGMI", "0")
+    assert bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1"]) == 0
+    plain = _json_lines(capsys.readouterr().out)
+    assert plain == [{"value": 1.0, "full": False}]
+    assert bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"]) == 0
+    full = _json_lines(capsys.readouterr().out)
+    assert len(full) == 1 and full[0]["full"] is True and full[0]["calibration"] == {"gemm_8192_bf16_tflops": 1.0}
+    assert full[0]["config2_8b_full"]["mb"] is None and full[0]["config2_8b_full_mb4"]["mb"] == 4

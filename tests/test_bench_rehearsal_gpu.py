@@ -44,7 +44,7 @@ def test_bench_multi_rank_flow_on_shared_gpu(gpu, world):
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     log = os.path.join(ROOT, "gpurun_out", f"bench_rehearsal_w{world}.log")  # progress a long run keeps writing
     cmd = [sys.executable, "bench.py", "--gpus", str(world), "--layers", "2", "--steps", "2", "--warmup", "1",
-           "--seq-len", "1024", "--config3", "on", "--config4", "on", "--config4-model", "tiny-d128",
+           "--seq-len", "1024", "--full", "--config3", "on", "--config4", "on", "--config4-model", "tiny-d128",
            "--config4-steps", "2", "--config4-warmup", "1", "--full-model", "tiny-d128", "--full-steps", "2",
            "--full-warmup", "1", "--no-calibrate", "--time-budget-s", "500", "--child-min-s", "40"]
     with open(log, "w") as f:

@@ -201,14 +201,22 @@ def test_bench_contract_tiny(gpu, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / "b.json"
     r = subprocess.run([sys.executable, "bench.py", "--model", "tiny-d128", "--steps", "2", "--warmup", "1",
-                        "--seq-len", "256", "--json-out", str(out)], cwd=root, capture_output=True, text=True,
-                       timeout=300)
+                        "--seq-len", "256", "--json-out", str(out), "--dump-outputs", str(tmp_path / "dump")],
+                       cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads(out.read_text())
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
         assert k in j
     assert j["value"] > 0 and j["n_gpus"] == 1
+    # a plain run (no --full) measures the headline only
+    assert "calibration" not in j and not j["gpu_after_timed_steps"] and not [k for k in j if k.startswith("config2")]
+    # --dump-outputs: the last step's loss and the parameters it trained, float32
+    import numpy as np
+
+    loss, w = np.load(tmp_path / "dump" / "loss.npy"), np.load(tmp_path / "dump" / "trained_params.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and abs(float(loss[0]) - j["final_loss"]) < 1e-3
+    assert w.dtype == np.float32 and w.size >= j["trainable_params"] and np.isfinite(w).all() and np.any(w != 0)
 
 
 def test_bench_two_ranks_on_one_gpu(gpu, tmp_path):

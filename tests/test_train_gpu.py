@@ -273,7 +273,7 @@ def test_bench_config2_field_tiny(gpu, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / "b.json"
     r = subprocess.run([sys.executable, "bench.py", "--model", "tiny-d128", "--steps", "2", "--warmup", "1",
-                        "--seq-len", "256", "--config2", "on", "--full-model", "tiny-d128", "--full-steps", "2",
+                        "--seq-len", "256", "--full", "--config2", "on", "--full-model", "tiny-d128", "--full-steps", "2",
                         "--full-warmup", "1", "--json-out", str(out)], cwd=root, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -282,6 +282,7 @@ def test_bench_config2_field_tiny(gpu, tmp_path):
     assert "error" not in c2, c2
     assert c2["value"] > 0 and "config 2" in c2["label"] and c2["config"]["finetune"].startswith("full")
     assert "overlapped" in c2["config"]["optimizer"]
+    assert "gemm_8192_bf16_tflops" in j["calibration"], j["calibration"]  # --full: the box calibration too
 
 
 @pytest.mark.parametrize("gbf16,zero", [(True, False), (True, True), (False, False)])
