@@ -638,13 +638,14 @@ std::tuple<at::Tensor, at::Tensor> ce_fwd_bwd(at::Tensor logits, const at::Tenso
   return {loss, losses};
 }
 
-// 1 / (number of labels != ignore) as a 1-element f32 device tensor (0 when none)
-at::Tensor ce_inv_count(const at::Tensor& labels, int64_t ignore) {
+// 1 / (number of rows the CE kernels count: label != ignore and inside [0, V)) as a 1-element f32
+// device tensor (0 when none)
+at::Tensor ce_inv_count(const at::Tensor& labels, int64_t ignore, int64_t V) {
   MX_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong, "labels must be int64 GPU");
   DevGuard g(labels.device());
   auto lab = labels.contiguous();
   auto inv = at::empty({1}, labels.options().dtype(at::kFloat));
-  MX_OK(mx_ce_inv_count(lab.data_ptr<int64_t>(), lab.numel(), ignore, inv.data_ptr<float>(), cur_stream()));
+  MX_OK(mx_ce_inv_count(lab.data_ptr<int64_t>(), lab.numel(), (int)V, ignore, inv.data_ptr<float>(), cur_stream()));
   return inv;
 }
 
@@ -1292,7 +1293,7 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("embedding_bwd(Tensor dy, Tensor ids, int V) -> Tensor");
   m.def("embedding_bwd_sorted(Tensor dy, Tensor sid, Tensor perm, Tensor(a!) out) -> ()");
   m.def("ce_fwd_bwd(Tensor(a!) logits, Tensor labels, int ignore_index) -> (Tensor, Tensor)");
-  m.def("ce_inv_count(Tensor labels, int ignore_index) -> Tensor");
+  m.def("ce_inv_count(Tensor labels, int ignore_index, int vocab) -> Tensor");
   m.def("ce_chunk(Tensor(a!) logits, Tensor labels, int ignore_index, Tensor inv_n) -> Tensor");
   m.def("ce_chunk_f32(Tensor logits, Tensor(a!) dl, Tensor labels, int ignore_index, Tensor inv_n) -> Tensor");
   m.def("rope_split(Tensor qkv, Tensor cos, Tensor sin, int B, int S, int Hq, int Hkv, int D, Tensor? positions=None) -> (Tensor, Tensor, Tensor)");

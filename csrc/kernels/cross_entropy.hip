@@ -7,7 +7,8 @@
 //   pass 2: re-read the row (served from the Infinity Cache: rows in flight
 //           x 256 KB << 256 MiB) and overwrite it with
 //           (softmax - onehot(label)) / n_valid  in bf16.
-// Rows whose label == ignore_index get loss 0 and a zero gradient row.
+// Rows whose label == ignore_index, or lies outside [0, V), get loss 0 and a zero gradient row
+// and do not count in n_valid (ce_row_ignored: one predicate for the count and the row kernels).
 // n_valid is counted on device first (no host sync anywhere).
 #include "common.h"
 
@@ -16,11 +17,15 @@ namespace mx {
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
-__global__ void __launch_bounds__(256) count_valid_kernel(const int64_t* __restrict__ labels, int64_t T,
+__device__ __forceinline__ bool ce_row_ignored(int64_t lab, int V, int64_t ignore) {
+  return lab == ignore || lab < 0 || lab >= V;
+}
+
+__global__ void __launch_bounds__(256) count_valid_kernel(const int64_t* __restrict__ labels, int64_t T, int V,
                                                           int64_t ignore, float* __restrict__ inv_n) {
   __shared__ float scratch[16];
   float c = 0.f;
-  for (int64_t i = threadIdx.x; i < T; i += 256) c += (labels[i] != ignore) ? 1.f : 0.f;
+  for (int64_t i = threadIdx.x; i < T; i += 256) c += ce_row_ignored(labels[i], V, ignore) ? 0.f : 1.f;
   c = block_sum(c, scratch);
   if (threadIdx.x == 0) inv_n[0] = c > 0.f ? 1.f / c : 0.f;
 }
@@ -35,7 +40,7 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(uint16_t* __restrict__ 
   uint16_t* x = logits + row * (int64_t)V;
   const int64_t lab = labels[row];
   const float inv_n = inv_n_p[0];
-  if (lab == ignore || lab < 0 || lab >= V) {
+  if (ce_row_ignored(lab, V, ignore)) {
     const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int c = threadIdx.x * 8; c < V; c += 256 * 8) *reinterpret_cast<u16x8*>(x + c) = z;
     if (threadIdx.x == 0) losses[row] = 0.f;
@@ -55,7 +60,10 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(uint16_t* __restrict__ 
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += exp2f(v[j] - nm);
-    s = s * exp2f(m - nm) + acc;
+    // nm == -inf: everything this lane has seen is -inf (a masked vocabulary range) and v - nm is NaN;
+    // the sum stays 0.  A select, as in the combine below, not a branch: the arithmetic of every
+    // other input stays in one block and compiles as before
+    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + acc;
     m = nm;
   }
   // combine (m, s) across the wave, then across waves
@@ -104,7 +112,7 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_f32_kernel(const float* __rest
   uint16_t* d = dl + row * (int64_t)V;
   const int64_t lab = labels[row];
   const float inv_n = inv_n_p[0];
-  if (lab == ignore || lab < 0 || lab >= V) {
+  if (ce_row_ignored(lab, V, ignore)) {
     const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int c = threadIdx.x * 8; c < V; c += 256 * 8) *reinterpret_cast<u16x8*>(d + c) = z;
     if (threadIdx.x == 0) losses[row] = 0.f;
@@ -124,7 +132,10 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_f32_kernel(const float* __rest
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += exp2f(v[j] - nm);
-    s = s * exp2f(m - nm) + acc;
+    // nm == -inf: everything this lane has seen is -inf (a masked vocabulary range) and v - nm is NaN;
+    // the sum stays 0.  A select, as in the combine below, not a branch: the arithmetic of every
+    // other input stays in one block and compiles as before
+    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + acc;
     m = nm;
   }
 #pragma unroll
@@ -175,7 +186,7 @@ using namespace mx;
 extern "C" int mx_ce_fwd_bwd(uint16_t* logits, const int64_t* labels, float* losses, float* inv_n, float* loss_out,
                              int64_t T, int V, int64_t ignore, hipStream_t stream) {
   if (V % 8 || T <= 0) return T <= 0 ? 0 : -1;
-  count_valid_kernel<<<1, 256, 0, stream>>>(labels, T, ignore, inv_n);
+  count_valid_kernel<<<1, 256, 0, stream>>>(labels, T, V, ignore, inv_n);
   ce_fwd_bwd_kernel<<<(unsigned)T, 256, 0, stream>>>(logits, labels, losses, inv_n, V, ignore);
   ce_reduce_kernel<<<1, 256, 0, stream>>>(losses, T, inv_n, loss_out);
   return (int)hipGetLastError();
@@ -183,9 +194,10 @@ extern "C" int mx_ce_fwd_bwd(uint16_t* logits, const int64_t* labels, float* los
 
 // Chunked LM head + CE (mxllm/ops/loss.py): the valid-token count over ALL chunks first, then one
 // fwd+bwd launch per chunk of rows against that global 1 / n_valid.
-extern "C" int mx_ce_inv_count(const int64_t* labels, int64_t T, int64_t ignore, float* inv_n, hipStream_t stream) {
+extern "C" int mx_ce_inv_count(const int64_t* labels, int64_t T, int V, int64_t ignore, float* inv_n,
+                               hipStream_t stream) {
   if (T <= 0) return 0;
-  count_valid_kernel<<<1, 256, 0, stream>>>(labels, T, ignore, inv_n);
+  count_valid_kernel<<<1, 256, 0, stream>>>(labels, T, V, ignore, inv_n);
   return (int)hipGetLastError();
 }
 

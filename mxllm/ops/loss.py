@@ -47,7 +47,7 @@ class _LinearCEFn(torch.autograd.Function):
         if _fp32_logits(False):
             lg32 = gemm.mm("tn", h, w, out_dtype=torch.float32)
             logits = torch.empty(lg32.shape, dtype=h.dtype, device=h.device)  # receives dlogits (bf16)
-            inv_n = native().ce_inv_count(labels, ignore_index)
+            inv_n = native().ce_inv_count(labels, ignore_index, w.shape[0])
             loss = native().ce_chunk_f32(lg32, logits, labels, ignore_index, inv_n).sum() * inv_n[0]
             del lg32
         else:
@@ -107,7 +107,7 @@ class _ChunkedLinearCEFn(torch.autograd.Function):
         # of the CALLER -- inside forward it is always off -- and an input that requires grad)
         need_h, need_w = grad_mode and ctx.needs_input_grad[0], grad_mode and ctx.needs_input_grad[1]
         if nat:
-            inv_n = native().ce_inv_count(labels, ignore_index)
+            inv_n = native().ce_inv_count(labels, ignore_index, V)
         else:
             inv_n = (1.0 / (labels != ignore_index).sum().clamp(min=1).float()).reshape(1)
         losses = torch.empty(T, dtype=torch.float32, device=h.device)
