@@ -6,7 +6,8 @@ each moves the ratio by a fraction of itself.  ``assert_parity`` bounds every el
 
     |out - ref| <= c_rel * |ref| + c_abs * scale
 
-``scale`` is the max |ref| of the element's row (last dimension) or of the whole tensor.  The
+``scale`` is the max |ref| of the element's row (last dimension) or of the whole tensor (or, for
+an output whose every element can cancel, a given magnitude of its operands).  The
 absolute term is there because some outputs cancel (RMSNorm dx, the cross-entropy gradient p - 1,
 the RoPE rotation): their error is relative to the operands, not to the result.
 
@@ -68,15 +69,70 @@ ROPE_DQKV_MEASURED = (0.00389, 2.08e-07)
 ROPE_DQKV = (ULP_BF16, 4.16e-07)  # 2 x 0.00389 < one ulp; 2 x 2.08e-07
 EMBEDDING_DW_MEASURED = (0, 5.12e-08)
 EMBEDDING_DW = (ULP_F32, 1.02e-07)  # 2 x 0 < one ulp; 2 x 5.12e-08
+# Attention (tests/test_attention_strict_gpu.py; ``python -m tests.test_attention_strict_gpu`` prints the
+# measurements): the fp32 model of the algorithm documented in attn_fwd.hip / attn_bwd.hip against fp64.
+# The abs terms are those of the documented bf16 roundings of P~, P and dS before their MFMA products,
+# not of fp32 arithmetic; O against its row, lse against the tensor, the gradients against the
+# magnitude of their operands (``scales`` there).
+ATTN_O_MEASURED = (0.00389, 0.00402)
+ATTN_O = (ULP_BF16, 0.00804)  # 2 x 0.00389 < one ulp; 2 x 0.00402
+ATTN_LSE_MEASURED = (0, 1.71e-07)
+ATTN_LSE = (ULP_F32, 3.42e-07)  # 2 x 0 < one ulp; 2 x 1.71e-07
+ATTN_DQ_MEASURED = (0, 0.00146)
+ATTN_DQ = (ULP_F32, 0.00292)  # 2 x 0 < one ulp; 2 x 0.00146
+ATTN_DK_MEASURED = (0, 0.00238)
+ATTN_DK = (ULP_F32, 0.00476)  # 2 x 0 < one ulp; 2 x 0.00238
+ATTN_DV_MEASURED = (0, 0.00204)
+ATTN_DV = (ULP_F32, 0.00408)  # 2 x 0 < one ulp; 2 x 0.00204
+ATTN_ROPE_DQKV_MEASURED = (0.00389, 0.00101)
+ATTN_ROPE_DQKV = (ULP_BF16, 0.00202)  # 2 x 0.00389 < one ulp; 2 x 0.00101
+
+
+def assert_exact(out: torch.Tensor, want: torch.Tensor, name: str = "") -> None:
+    """Assert ``torch.equal(out, want)``: same shape, same dtype, every element equal (no tolerance).
+
+    For the cases whose result is exactly representable whatever the summation order (integer
+    operands of an MFMA GEMM, a one-hot softmax).  On failure the message gives the mismatch count,
+    the first and the worst mismatch with both values, and the bounding box of the mismatches over
+    the last two dimensions -- rows a..b, columns c..d name the wrong fragment, tile or row."""
+    assert tuple(out.shape) == tuple(want.shape), f"{name}: shape {tuple(out.shape)} vs expected {tuple(want.shape)}"
+    assert out.dtype == want.dtype, f"{name}: dtype {out.dtype} vs expected {want.dtype}"
+    if torch.equal(out, want):
+        return
+    o, w = out.detach().to(torch.float64), want.detach().to(torch.float64)
+    bad = ~(o == w)  # NaN compares false: counted
+    diff = torch.where(torch.isfinite(o - w), (o - w).abs(), torch.full_like(o, float("inf")))
+    diff = torch.where(bad, diff, torch.zeros_like(diff))
+    nz = bad.nonzero()
+    first = tuple(int(i) for i in nz[0])
+    flat = int(diff.reshape(-1).argmax())
+    worst = []
+    for d in reversed(o.shape):
+        worst.append(flat % d)
+        flat //= d
+    worst = tuple(reversed(worst))
+    box = ""
+    if o.dim() >= 2:
+        r, c = nz[:, -2], nz[:, -1]
+        box = f"; rows {int(r.min())}..{int(r.max())}, columns {int(c.min())}..{int(c.max())}"
+        if o.dim() > 2:
+            lead = sorted({tuple(int(i) for i in row) for row in nz[:, :-2].tolist()})
+            box += f" of {len(lead)} leading index(es) from {lead[0]} to {lead[-1]}"
+    elif o.dim() == 1:
+        box = f"; indices {int(nz.min())}..{int(nz.max())}"
+    raise AssertionError(
+        f"{name or 'output'}: {int(bad.sum())} of {o.numel()} elements differ; first at {first}: out "
+        f"{o[first].item():.9g}, expected {w[first].item():.9g}; worst at {worst}: out {o[worst].item():.9g}, "
+        f"expected {w[worst].item():.9g}{box}")
 
 
 def assert_parity(out: torch.Tensor, ref: torch.Tensor, bound, *, scale: str = "row", name: str = "") -> None:
     """Assert ``|out - ref| <= c_rel |ref| + c_abs scale`` for every element.
 
     ``out``: the kernel's output (any float dtype).  ``ref``: the fp64 reference, same shape, same
-    device.  ``bound``: ``(c_rel, c_abs)``.  ``scale``: ``"row"`` (max |ref| over the last dimension)
-    or ``"tensor"``.  A non-finite ``out`` element fails.  On failure the message names the worst
-    element (largest excess over its bound), both values there, and how many elements exceed the
+    device.  ``bound``: ``(c_rel, c_abs)``.  ``scale``: ``"row"`` (max |ref| over the last dimension),
+    ``"tensor"``, or a number: the magnitude of the operands of an output that can cancel as a
+    whole.  A non-finite ``out`` element fails.  On failure the message names the worst element (largest excess over its bound), both values there, and how many elements exceed the
     bound -- which localizes a wrong chunk, row or block."""
     c_rel, c_abs = bound
     assert ref.dtype == torch.float64, "the reference must be fp64"
@@ -86,9 +142,12 @@ def assert_parity(out: torch.Tensor, ref: torch.Tensor, bound, *, scale: str = "
     o = out.detach().to(torch.float64)
     r = ref.detach()
     if scale == "row":
-        s = r.abs().amax(dim=-1, keepdim=True)
+        s, what = r.abs().amax(dim=-1, keepdim=True), "row-max"
     elif scale == "tensor":
-        s = r.abs().max()
+        s, what = r.abs().max(), "tensor-max"
+    elif isinstance(scale, (float, torch.Tensor)):
+        s = torch.as_tensor(scale, dtype=torch.float64, device=r.device)
+        what = f"x {float(s):.3g} (operand magnitude)"
     else:
         raise ValueError(scale)
     err = (o - r).abs()
@@ -107,6 +166,6 @@ def assert_parity(out: torch.Tensor, ref: torch.Tensor, bound, *, scale: str = "
     first = tuple(int(i) for i in bad.nonzero()[0])
     raise AssertionError(
         f"{name or 'output'}: {nbad} of {o.numel()} elements exceed |out - ref| <= {c_rel:.3g} |ref| + "
-        f"{c_abs:.3g} {scale}-max; worst at {idx}: out {o[idx].item():.9g}, ref {r[idx].item():.9g}, "
+        f"{c_abs:.3g} {what}; worst at {idx}: out {o[idx].item():.9g}, ref {r[idx].item():.9g}, "
         f"|diff| {err[idx].item():.3g} > bound {lim.expand_as(err)[idx].item():.3g}; first at {first}")
 
