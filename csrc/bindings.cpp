@@ -1043,6 +1043,76 @@ at::Tensor sample_rows(const at::Tensor& logits, const at::Tensor& temps, const 
   return out;
 }
 
+// sampling penalties + logit_bias on the logits (logits_proc.hip): f32 [B, V].  state int32
+// [n_slots, V] / bias f32 [n_slots, V] may be absent; slots < 0: plain conversion
+at::Tensor logits_adjust_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& state,
+                              const at::Tensor& slots, const at::Tensor& presence, const at::Tensor& frequency,
+                              const at::Tensor& repetition, const c10::optional<at::Tensor>& bias) {
+  MX_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "logits [B, V] contiguous GPU");
+  MX_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16/f32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  auto chk = [&](const at::Tensor& t, at::ScalarType st, const char* name) {
+    MX_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st && t.numel() == B, name);
+  };
+  chk(slots, at::kInt, "slots i32 [B]");
+  chk(presence, at::kFloat, "presence f32 [B]");
+  chk(frequency, at::kFloat, "frequency f32 [B]");
+  chk(repetition, at::kFloat, "repetition f32 [B]");
+  int64_t n_slots = -1;
+  auto table = [&](const c10::optional<at::Tensor>& t, at::ScalarType st, const char* name) {
+    if (!t.has_value()) return;
+    MX_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == st && t->dim() == 2 && t->size(1) == V &&
+                 (n_slots < 0 || t->size(0) == n_slots), name);
+    n_slots = t->size(0);
+  };
+  table(state, at::kInt, "state i32 [n_slots, V]");
+  table(bias, at::kFloat, "bias f32 [n_slots, V]");
+  DevGuard g(logits.device());
+  auto out = at::empty({B, V}, logits.options().dtype(at::kFloat));
+  MX_OK(mx_logits_adjust_rows(logits.data_ptr(), logits.scalar_type() == at::kBFloat16 ? 1 : 0,
+                              out.data_ptr<float>(), (int)B, (int)V,
+                              state.has_value() ? state->data_ptr<int32_t>() : nullptr, slots.data_ptr<int32_t>(),
+                              (int)std::max<int64_t>(n_slots, 0), presence.data_ptr<float>(),
+                              frequency.data_ptr<float>(), repetition.data_ptr<float>(),
+                              bias.has_value() ? bias->data_ptr<float>() : nullptr, cur_stream()));
+  return out;
+}
+
+// state[slots[b], ids[b]] += 1 in place (slots < 0 skipped)
+void token_state_update(at::Tensor state, const at::Tensor& slots, const at::Tensor& ids) {
+  MX_CHECK(state.is_cuda() && state.is_contiguous() && state.scalar_type() == at::kInt && state.dim() == 2,
+           "state i32 [n_slots, V] contiguous GPU");
+  const int64_t B = slots.numel();
+  MX_CHECK(slots.is_cuda() && slots.is_contiguous() && slots.scalar_type() == at::kInt, "slots i32 [B]");
+  MX_CHECK(ids.is_cuda() && ids.is_contiguous() && ids.scalar_type() == at::kLong && ids.numel() == B, "ids i64 [B]");
+  DevGuard g(state.device());
+  MX_OK(mx_token_state_update(state.data_ptr<int32_t>(), slots.data_ptr<int32_t>(), ids.data_ptr<int64_t>(), (int)B,
+                              (int)state.size(1), (int)state.size(0), cur_stream()));
+}
+
+// log-probabilities of the chosen and the n_top[b] most likely tokens of every row (logits_proc.hip)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_rows(const at::Tensor& logits, const at::Tensor& ids,
+                                                            const at::Tensor& n_top) {
+  MX_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "logits [B, V] contiguous GPU");
+  MX_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16/f32");
+  const int64_t B = logits.size(0);
+  MX_CHECK(ids.is_cuda() && ids.is_contiguous() && ids.scalar_type() == at::kLong && ids.numel() == B, "ids i64 [B]");
+  MX_CHECK(n_top.is_cuda() && n_top.is_contiguous() && n_top.scalar_type() == at::kInt && n_top.numel() == B,
+           "n_top i32 [B]");
+  DevGuard g(logits.device());
+  auto chosen = at::empty({B}, logits.options().dtype(at::kFloat));
+  auto top_ids = at::empty({B, 20}, logits.options().dtype(at::kInt));
+  auto top_lp = at::empty({B, 20}, logits.options().dtype(at::kFloat));
+  MX_CHECK(B <= 65535 && logits.size(1) <= 2048 * 400, "logprob_rows: at most 65535 rows of at most 819200 logits");
+  // per-call slice candidates / partial sums (stream-ordered allocator)
+  auto ws = at::empty({std::max<int64_t>(1, (mx_logprob_ws_bytes((int)B, (int)logits.size(1)) + 7) / 8)},
+                      logits.options().dtype(at::kLong));
+  MX_OK(mx_logprob_rows(logits.data_ptr(), logits.scalar_type() == at::kBFloat16 ? 1 : 0, ids.data_ptr<int64_t>(),
+                        n_top.data_ptr<int32_t>(), chosen.data_ptr<float>(), top_ids.data_ptr<int32_t>(),
+                        top_lp.data_ptr<float>(), (int)B, (int)logits.size(1), ws.data_ptr(), cur_stream()));
+  return {chosen, top_ids, top_lp};
+}
+
 }  // namespace
 
 
@@ -1306,6 +1376,10 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("sample(Tensor logits, float temperature, int seed, int step) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temps, Tensor top_p, Tensor top_k, Tensor seeds, Tensor steps) -> Tensor");
   m.def("sample_temp_rows(Tensor logits, Tensor temps, Tensor seeds, Tensor steps) -> Tensor");
+  m.def("logits_adjust_rows(Tensor logits, Tensor? state, Tensor slots, Tensor presence, Tensor frequency, "
+        "Tensor repetition, Tensor? bias) -> Tensor");
+  m.def("token_state_update(Tensor(a!) state, Tensor slots, Tensor ids) -> ()");
+  m.def("logprob_rows(Tensor logits, Tensor ids, Tensor n_top) -> (Tensor, Tensor, Tensor)");
   m.def("w8_linear(Tensor x, Tensor q, Tensor scale) -> Tensor");
   m.def("skinny_linear(Tensor x, Tensor w) -> Tensor");
   m.def("skinny_linear_swiglu(Tensor x, Tensor w) -> Tensor");
@@ -1362,6 +1436,9 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("sample_rows", &sample_rows);
   m.impl("sample_temp_rows", &sample_temp_rows);
+  m.impl("logits_adjust_rows", &logits_adjust_rows);
+  m.impl("token_state_update", &token_state_update);
+  m.impl("logprob_rows", &logprob_rows);
   m.impl("w8_linear", &w8_linear);
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny_linear_swiglu", &skinny_linear_swiglu);

@@ -109,6 +109,15 @@ int mx_sample_temp_rows(const void* logits, int is_bf16, int64_t* out, int B, in
 int mx_sample_rows(const void* logits, int is_bf16, int64_t* out, int B, int V, const float* temps,
                    const float* top_ps, const int32_t* top_ks, const int64_t* seeds, const int32_t* steps,
                    hipStream_t stream);
+// logits_proc.hip
+int mx_logits_adjust_rows(const void* logits, int is_bf16, float* out, int B, int V, const int32_t* state,
+                          const int32_t* slots, int n_slots, const float* presence, const float* frequency,
+                          const float* repetition, const float* bias, hipStream_t stream);
+int mx_token_state_update(int32_t* state, const int32_t* slots, const int64_t* ids, int B, int V, int n_slots,
+                          hipStream_t stream);
+int64_t mx_logprob_ws_bytes(int B, int V);
+int mx_logprob_rows(const void* logits, int is_bf16, const int64_t* ids, const int32_t* n_top, float* chosen_lp,
+                    int32_t* top_ids, float* top_lp, int B, int V, void* ws, hipStream_t stream);
 }
 
 extern "C" {

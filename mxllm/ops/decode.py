@@ -1,7 +1,8 @@
 """Inference ops: prefill attention into a KV cache, decode attention, sampling.
 
 GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, greedy /
-Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature) and
+Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature),
+logits_proc.hip (sampling penalties, logit_bias, log-probabilities) and
 attn_fwd.hip for prefill.  CPU: reference implementations.
 """
 from __future__ import annotations
@@ -157,3 +158,110 @@ def filter_probs(row: torch.Tensor, temperature: float, top_k: int = 0, top_p: f
         keep &= p >= cut
         p = torch.softmax(x.masked_fill(~keep, float("-inf")), -1)
     return p
+
+
+# ---------------------------------------------------------------- penalties, logit_bias, logprobs
+# Token state of a request (int32 [n_slots, V]): bits 0..30 count the token's occurrences in
+# the request's output, bit 31 says that it occurs in the prompt.
+PROMPT_FLAG = -(1 << 31)
+COUNT_MASK = 0x7FFFFFFF
+TOP_LOGPROBS_MAX = 20
+
+
+def _row_param(v, dtype, device) -> torch.Tensor:
+    if isinstance(v, torch.Tensor):
+        return v.to(device=device, dtype=dtype).contiguous()
+    t = torch.tensor(list(v), dtype=dtype)
+    if device.type == "cuda":
+        t = t.pin_memory().to(device, non_blocking=True)
+    return t
+
+
+def adjust_logits_rows(logits: torch.Tensor, state, slots, presence, frequency, repetition,
+                       bias=None) -> torch.Tensor:
+    """Sampling penalties and logit_bias: logits [B, V] (bf16 / f32) -> f32 [B, V].
+
+    ``state`` int32 [n_slots, V] (``PROMPT_FLAG`` / ``COUNT_MASK``; None: no token seen), ``bias``
+    f32 [n_slots, V] or None, ``slots`` [B] the row of both tables that belongs to each logits row
+    (< 0: the row is only converted), ``presence`` / ``frequency`` / ``repetition`` [B].
+    Per element, in this order, every fp32 operation rounded on its own:
+
+      1. x = float(logit)
+      2. token in the prompt or the output, repetition != 1: x = x / repetition if x > 0 else
+         x * repetition  (HF / vLLM repetition penalty: prompt and output tokens)
+      3. output count c > 0: x = x - (frequency * float(c) + presence)  (OpenAI: output tokens only)
+      4. bias != 0: x = x + bias
+
+    An element that no step touches is the input converted to f32 bit for bit (-0.0 stays -0.0).
+    GPU: one elementwise launch (csrc/kernels/logits_proc.hip); the CPU expression below gives the
+    same bits."""
+    dev = logits.device
+    sl = _row_param(slots, torch.int32, dev)
+    pres = _row_param(presence, torch.float32, dev)
+    freq = _row_param(frequency, torch.float32, dev)
+    rep = _row_param(repetition, torch.float32, dev)
+    if use_native(logits):
+        x = logits if logits.dtype in (torch.bfloat16, torch.float32) else logits.float()
+        return native().logits_adjust_rows(x.contiguous(), state, sl, pres, freq, rep, bias)
+    x = logits.float().clone()
+    B, V = x.shape
+    live = (sl >= 0).view(B, 1)
+    idx = sl.clamp(min=0).long()
+    if state is not None:
+        st = state[idx]
+        cnt = st & COUNT_MASK
+        r = rep.view(B, 1).expand(B, V)
+        pen = torch.where(x > 0, x / r, x * r)
+        x = torch.where(live & (st != 0) & (r != 1), pen, x)
+        sub = x - (freq.view(B, 1) * cnt.float() + pres.view(B, 1))
+        x = torch.where(live & (cnt > 0), sub, x)
+    if bias is not None:
+        bb = bias[idx]
+        x = torch.where(live & (bb != 0), x + bb, x)
+    return x
+
+
+def token_state_update(state: torch.Tensor, slots, ids: torch.Tensor) -> None:
+    """Count the tokens just drawn: ``state[slots[b], ids[b]] += 1`` in place (rows with
+    ``slots[b] < 0`` skipped)."""
+    sl = _row_param(slots, torch.int32, state.device)
+    if use_native(state):
+        native().token_state_update(state, sl, ids.to(state.device, torch.long).contiguous())
+        return
+    for s_, t in zip(sl.tolist(), ids.tolist()):
+        if s_ >= 0:
+            state[s_, t] += 1
+
+
+def logprob_rows(logits: torch.Tensor, ids: torch.Tensor, n_top):
+    """Log-probabilities of the chosen token ``ids[b]`` and of the ``n_top[b]`` most likely
+    tokens of every logits row: (chosen_lp f32 [B], top_ids int32 [B, 20], top_lp f32 [B, 20]).
+
+    fp32 log-softmax: lse = max + log(sum exp(x - max)), logprob = x - lse.  The top list is in
+    descending order, ties broken by the LOWER token id (the greedy sampler's rule, so for a
+    greedy row top_ids[:, 0] is the sampled id and top_lp[:, 0] == chosen_lp bit for bit).
+    ``n_top[b]`` in 0..20; -1 skips the row.  Skipped rows and entries beyond ``n_top`` hold
+    -1 / -inf.  GPU: csrc/kernels/logits_proc.hip, one workgroup per row, no float atomics."""
+    dev = logits.device
+    nt = _row_param(n_top, torch.int32, dev)
+    if use_native(logits):
+        x = logits if logits.dtype in (torch.bfloat16, torch.float32) else logits.float()
+        return native().logprob_rows(x.contiguous(), ids.to(dev, torch.long).contiguous(), nt)
+    x = logits.float()
+    B, V = x.shape
+    chosen = torch.full((B,), float("-inf"))
+    top_ids = torch.full((B, TOP_LOGPROBS_MAX), -1, dtype=torch.int32)
+    top_lp = torch.full((B, TOP_LOGPROBS_MAX), float("-inf"))
+    for b, n in enumerate(nt.tolist()):
+        if n < 0:
+            continue
+        row = x[b]
+        mx = row.max()
+        lse = mx + torch.log(torch.exp(row - mx).sum())
+        chosen[b] = row[int(ids[b])] - lse
+        n = min(n, TOP_LOGPROBS_MAX, V)
+        if n > 0:
+            order = torch.sort(row, descending=True, stable=True).indices[:n]  # equal values: lower id first
+            top_ids[b, :n] = order.to(torch.int32)
+            top_lp[b, :n] = row[order] - lse
+    return chosen, top_ids, top_lp

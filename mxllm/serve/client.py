@@ -54,6 +54,7 @@ class Choice:
     message: Message
     index: int = 0
     finish_reason: str | None = "stop"
+    logprobs: dict | None = None  # OpenAI chat shape {"content": [...]} when asked for
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -73,6 +74,7 @@ class StreamChoice:
     delta: Delta
     index: int = 0
     finish_reason: str | None = None
+    logprobs: dict | None = None  # the entries of this chunk's tokens
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -115,13 +117,60 @@ def _local_engine(model: str):
     raise CompletionError(f"no local engine registered for model {model!r}")
 
 
+# request fields forwarded to an HTTP endpoint besides model / messages / max_tokens / temperature
+_FORWARD = ("top_p", "stop", "seed", "top_k", "presence_penalty", "frequency_penalty", "repetition_penalty",
+            "logit_bias", "logprobs", "top_logprobs")
+
+
+def _engine_kw(kw, chat: bool) -> dict:
+    """The engine's keywords for the penalty / bias / logprobs fields of a request (in-process
+    routes).  Chat: ``logprobs`` a boolean + ``top_logprobs``; completions: ``logprobs`` an int."""
+    if chat:
+        lp = (int(kw.get("top_logprobs") or 0) if kw.get("logprobs") else None)
+    else:
+        lp = kw.get("logprobs")
+    bias = kw.get("logit_bias")
+    return {"presence_penalty": kw.get("presence_penalty") or 0.0,
+            "frequency_penalty": kw.get("frequency_penalty") or 0.0,
+            "repetition_penalty": 1.0 if kw.get("repetition_penalty") is None else kw["repetition_penalty"],
+            "logit_bias": {int(k): v for k, v in bias.items()} if bias else None, "logprobs": lp}
+
+
+def _tok_entry(tok, t, lp) -> dict:
+    s = tok.decode([t])
+    return {"token": s, "logprob": lp, "bytes": list(s.encode("utf-8"))}
+
+
+def _chat_logprobs(tok, toks, entries) -> dict:
+    return {"content": [dict(_tok_entry(tok, t, e[0]), top_logprobs=[_tok_entry(tok, i, l) for i, l in e[1]])
+                        for t, e in zip(toks, entries)]}
+
+
+def _text_logprobs(tok, toks, entries) -> dict:
+    out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+    off = 0
+    for t, e in zip(toks, entries):
+        s = tok.decode([t])
+        out["tokens"].append(s)
+        out["token_logprobs"].append(e[0])
+        out["top_logprobs"].append({tok.decode([i]): l for i, l in e[1]})
+        out["text_offset"].append(off)
+        off += len(s)
+    return out
+
+
 def _local(model, messages, max_tokens, temperature, **kw) -> ModelResponse:
     eng, tok = _local_engine(model)
     ids = tok.apply_chat_template(messages)
-    out = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature,
-                       top_p=kw.get("top_p", 1.0), seed=kw.get("seed", 0))[0]
+    ekw = _engine_kw(kw, chat=True)
+    r = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature,
+                     top_p=kw.get("top_p", 1.0), seed=kw.get("seed", 0), return_requests=True, **ekw)[0]
+    if r.error:
+        raise CompletionError(f"local engine: {r.error}")
+    out = r.output
     text = tok.decode([t for t in out if t not in eng.eos_ids])
-    return ModelResponse([Choice(Message(text))], model=model,
+    lp = _chat_logprobs(tok, out, r.logprobs) if ekw["logprobs"] is not None else None
+    return ModelResponse([Choice(Message(text), logprobs=lp)], model=model,
                          usage={"prompt_tokens": len(ids), "completion_tokens": len(out)})
 
 
@@ -168,7 +217,7 @@ def _http(model, messages, base, key, timeout, max_tokens, temperature, **kw) ->
     if key:
         headers["Authorization"] = f"Bearer {key}"
     body = {"model": model, "messages": messages, "max_tokens": max_tokens, "temperature": temperature}
-    body.update({k: v for k, v in kw.items() if k in ("top_p", "stop", "seed", "top_k")})
+    body.update({k: v for k, v in kw.items() if k in _FORWARD})
     r = httpx.post(url, json=body, headers=headers, timeout=timeout)
     if r.status_code == 429 or r.status_code >= 500:
         raise _Retryable(f"HTTP {r.status_code}: {r.text[:200]}")
@@ -176,7 +225,7 @@ def _http(model, messages, base, key, timeout, max_tokens, temperature, **kw) ->
         raise CompletionError(f"HTTP {r.status_code}: {r.text[:200]}")
     j = r.json()
     ch = [Choice(Message(c["message"]["content"], c["message"].get("role", "assistant")), c.get("index", i),
-                 c.get("finish_reason")) for i, c in enumerate(j["choices"])]
+                 c.get("finish_reason"), c.get("logprobs")) for i, c in enumerate(j["choices"])]
     return ModelResponse(ch, model=j.get("model", model), usage=j.get("usage", {}), id=j.get("id", ""))
 
 
@@ -195,16 +244,20 @@ def _local_stream(model, messages, max_tokens, temperature, **kw):
     eng, tok = _local_engine(model)
     eng.start()
     ids = tok.apply_chat_template(messages)
+    ekw = _engine_kw(kw, chat=True)
     r = eng.submit(ids, SamplingParams(max_new_tokens=max_tokens, temperature=temperature,
-                                       top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0), seed=kw.get("seed", 0)))
+                                       top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0), seed=kw.get("seed", 0),
+                                       **ekw))
     sent, first = 0, True
     while True:
         done = r.done.wait(0.002)
         toks = r.output[sent:]
         if toks:
+            lp = _chat_logprobs(tok, toks, r.logprobs[sent:sent + len(toks)]) if ekw["logprobs"] is not None else None
             sent += len(toks)
             text = tok.decode([t for t in toks if t not in eng.eos_ids])
-            yield ModelResponse([StreamChoice(Delta(text, "assistant" if first else None))], model=model)
+            yield ModelResponse([StreamChoice(Delta(text, "assistant" if first else None), logprobs=lp)],
+                                model=model)
             first = False
         if done and sent >= len(r.output):
             break
@@ -227,7 +280,7 @@ def _http_stream(model, messages, base, key, timeout, max_tokens, temperature, *
         headers["Authorization"] = f"Bearer {key}"
     body = {"model": model, "messages": messages, "max_tokens": max_tokens, "temperature": temperature,
             "stream": True}
-    body.update({k: v for k, v in kw.items() if k in ("top_p", "stop", "seed", "top_k")})
+    body.update({k: v for k, v in kw.items() if k in _FORWARD})
     with httpx.stream("POST", url, json=body, headers=headers, timeout=timeout) as r:
         if r.status_code != 200:
             r.read()
@@ -242,7 +295,8 @@ def _http_stream(model, messages, base, key, timeout, max_tokens, temperature, *
             ch = j["choices"][0]
             d = ch.get("delta") or {}
             yield ModelResponse([StreamChoice(Delta(d.get("content"), d.get("role")), ch.get("index", 0),
-                                              ch.get("finish_reason"))], model=j.get("model", model),
+                                              ch.get("finish_reason"), ch.get("logprobs"))],
+                                model=j.get("model", model),
                                 id=j.get("id", ""))
 
 
@@ -365,6 +419,7 @@ class TextChoice:
     text: str
     index: int = 0
     finish_reason: str | None = "stop"
+    logprobs: dict | None = None  # OpenAI completions shape {"tokens", "token_logprobs", ...}
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -377,10 +432,16 @@ def text_completion(model: str, prompt: str, *, api_base: str | None = None, api
     if _is_local(base):
         eng, tok = _local_engine(model)
         ids = tok.encode(prompt)
-        out = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature, top_p=kw.get("top_p", 1.0),
-                           top_k=kw.get("top_k", 0), seed=kw.get("seed", 0))[0]
+        ekw = _engine_kw(kw, chat=False)
+        r = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature, top_p=kw.get("top_p", 1.0),
+                         top_k=kw.get("top_k", 0), seed=kw.get("seed", 0), return_requests=True, **ekw)[0]
+        if r.error:
+            raise CompletionError(f"local engine: {r.error}")
+        out = r.output
         text = tok.decode([t for t in out if t not in eng.eos_ids])
-        return ModelResponse([TextChoice(text, finish_reason="length" if len(out) >= max_tokens else "stop")],
+        lp = _text_logprobs(tok, out, r.logprobs) if ekw["logprobs"] is not None else None
+        return ModelResponse([TextChoice(text, finish_reason="length" if len(out) >= max_tokens else "stop",
+                                         logprobs=lp)],
                              model=model, usage={"prompt_tokens": len(ids), "completion_tokens": len(out)})
     import httpx
 
@@ -390,11 +451,11 @@ def text_completion(model: str, prompt: str, *, api_base: str | None = None, api
         url += "/completions"
     headers = {"Authorization": f"Bearer {key}"} if key else {}
     body = {"model": model, "prompt": prompt, "max_tokens": max_tokens, "temperature": temperature}
-    body.update({k: v for k, v in kw.items() if k in ("top_p", "stop", "seed", "top_k")})
+    body.update({k: v for k, v in kw.items() if k in _FORWARD})
     r = httpx.post(url, json=body, headers=headers, timeout=timeout if timeout is not None else request_timeout)
     if r.status_code != 200:
         raise CompletionError(f"HTTP {r.status_code}: {r.text[:200]}")
     j = r.json()
     c = j["choices"][0]
-    return ModelResponse([TextChoice(c.get("text", ""), c.get("index", 0), c.get("finish_reason"))],
+    return ModelResponse([TextChoice(c.get("text", ""), c.get("index", 0), c.get("finish_reason"), c.get("logprobs"))],
                          model=j.get("model", model), usage=j.get("usage", {}))

@@ -68,6 +68,19 @@ class SamplingParams:
     top_k: int = 0
     stop_ids: tuple = ()
     seed: int = 0
+    # Sampling penalties, logit_bias and logprobs (mxllm/ops/decode.py adjust_logits_rows /
+    # logprob_rows).  Each logits row is edited in this order: repetition penalty (HF / vLLM:
+    # tokens of the prompt AND the output, x / r if x > 0 else x * r), then
+    # frequency * count + presence subtracted (OpenAI: tokens of the output only), then
+    # logit_bias added.  ``logprobs``: None = off, else the number (0..20) of most likely tokens
+    # listed per output token besides the chosen token's own log-probability.  The
+    # log-probabilities are the log-softmax of the logits AFTER penalties and bias and BEFORE
+    # temperature and the top-k / top-p cut; ties in the top list go to the lower token id.
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
+    logit_bias: dict | None = None
+    logprobs: int | None = None
 
     def __post_init__(self):
         if not (self.top_p == self.top_p and self.temperature == self.temperature):
@@ -76,6 +89,38 @@ class SamplingParams:
             raise ValueError(f"top_p must be in [0, 1] (0 = greedy), got {self.top_p}")
         if self.max_new_tokens < 0:
             raise ValueError(f"max_new_tokens must be >= 0, got {self.max_new_tokens}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float)) and -2.0 <= v <= 2.0):
+                raise ValueError(f"{name} must be in [-2, 2], got {v!r}")
+        r = self.repetition_penalty
+        if not (isinstance(r, (int, float)) and 0.0 < r < float("inf")):
+            raise ValueError(f"repetition_penalty must be > 0, got {r!r}")
+        if self.logit_bias is not None:
+            if not isinstance(self.logit_bias, dict) or len(self.logit_bias) > 300:
+                raise ValueError("logit_bias must be a dict of at most 300 token ids")
+            bias = {}
+            for k, v in self.logit_bias.items():
+                try:
+                    k = int(k)
+                except (TypeError, ValueError):
+                    raise ValueError(f"logit_bias key {k!r} is not a token id") from None
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= v <= 100.0:
+                    raise ValueError(f"logit_bias values must be in [-100, 100], got {v!r}")
+                bias[k] = float(v)
+            self.logit_bias = bias or None
+        if self.logprobs is not None:
+            if isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int) or not 0 <= self.logprobs <= 20:
+                raise ValueError(f"logprobs must be None or in 0..20, got {self.logprobs!r}")
+
+    @property
+    def penalised(self) -> bool:
+        """Needs the per-request token counts."""
+        return self.presence_penalty != 0 or self.frequency_penalty != 0 or self.repetition_penalty != 1
+
+    @property
+    def adjusts(self) -> bool:
+        return self.penalised or bool(self.logit_bias)
 
 
 @dataclass
@@ -91,6 +136,12 @@ class Request:
     t_first: float | None = None
     t_done: float | None = None
     error: str | None = None
+    # one (logprob, [(token id, logprob), ...]) per output token when params.logprobs is set
+    logprobs: list = field(default_factory=list)
+
+    def __post_init__(self):
+        # any penalty / logit_bias / logprobs: the request takes the adjusted sampling path
+        self.special = self.params.adjusts or self.params.logprobs is not None
 
 
 class Engine:
@@ -165,6 +216,11 @@ class Engine:
         self._tasks: list = []  # (fn, result box, event): run by the engine thread between steps
         self.steps = 0
         self.tokens_generated = 0
+        # sampling penalties / logit_bias (``_admit_state``): allocated when the first request that
+        # needs each is admitted.  int32 [max_batch, vocab] token state and f32 [max_batch, vocab] bias
+        self.vocab = getattr(model, "tp_vocab", c.vocab_size)
+        self._tok_state = None
+        self._tok_bias = None
         # latency / throughput counters: exported by the server's
         # /metrics and by stats()
         self.prefill_tokens = 0
@@ -589,6 +645,13 @@ class Engine:
                 need = len(r.prompt) + r.params.max_new_tokens
                 if not self.kv.fits_at_all(need):  # larger than the whole KV pool
                     self.waiting.pop(0)
+                    r.error = f"request needs {need} KV positions, more than the pool"
+                    rejected.append(r)
+                    continue
+                bad = [t for t in (r.params.logit_bias or ()) if not 0 <= t < self.vocab]
+                if bad:
+                    self.waiting.pop(0)
+                    r.error = f"logit_bias token id {bad[0]} outside the vocabulary [0, {self.vocab})"
                     rejected.append(r)
                     continue
                 if not self.kv.can_reserve(need):  # paged pool full: wait for finishing requests
@@ -598,10 +661,11 @@ class Engine:
                 self.kv.reserve(r.slot, need)
                 admit.append(r)
         for r in rejected:
-            r.error = f"request needs {len(r.prompt) + r.params.max_new_tokens} KV positions, more than the pool"
             self._finish(r, "error")
         if getattr(self, "tp_sync", False):
             admit = self._sync_admit(admit)
+        for r in admit:
+            self._admit_state(r)
         # admitted prompts are prefilled together, in groups of at most
         # prefill_tokens tokens (bounds the activation memory of one pass)
         groups, cur, ntok = [], [], 0
@@ -645,31 +709,151 @@ class Engine:
             self._accept(r, int(t))
         return True
 
-    @staticmethod
-    def _sample(logits: torch.Tensor, reqs, first: bool = False) -> list[int]:
+    def _admit_state(self, r: Request) -> None:
+        """Device state of a request that uses a penalty or a logit_bias: its slot's rows of
+        the token state (prompt flags set, counts zero) and of the bias table.  Both tables
+        are allocated by the first request that needs them; a request that needs neither
+        touches nothing."""
+        p = r.params
+        if not p.adjusts:
+            return
+        if p.penalised and self._tok_state is None:
+            self._tok_state = torch.zeros(self.max_batch, self.vocab, dtype=torch.int32, device=self.device)
+        if p.logit_bias and self._tok_bias is None:
+            self._tok_bias = torch.zeros(self.max_batch, self.vocab, dtype=torch.float32, device=self.device)
+        # an adjusted row reads its slot's row of both tables: clear what an earlier tenant left
+        if self._tok_state is not None:
+            self._tok_state[r.slot].zero_()
+            if p.penalised:
+                seen = sorted({t for t in r.prompt if 0 <= t < self.vocab})
+                if seen:
+                    self._tok_state[r.slot, torch.tensor(seen, device=self.device)] = dops.PROMPT_FLAG
+        if self._tok_bias is not None:
+            self._tok_bias[r.slot].zero_()
+            if p.logit_bias:
+                ids = torch.tensor(list(p.logit_bias), device=self.device)
+                self._tok_bias[r.slot, ids] = torch.tensor(list(p.logit_bias.values()), dtype=torch.float32,
+                                                           device=self.device)
+
+    def _sample(self, logits: torch.Tensor, reqs, first: bool = False) -> list[int]:
         """One batched draw for every row of ``logits`` with each request's own
         temperature / top-k / top-p; per-request RNG stream keyed by (seed, token
-        index), so draws do not depend on batching.  One host read-back."""
+        index), so draws do not depend on batching.  One host read-back.
+
+        A batch in which some request uses a penalty, a logit_bias or logprobs: the logits
+        are adjusted (``dops.adjust_logits_rows``, f32; skipped when only logprobs are asked
+        for), sampled, the drawn tokens counted for the penalised rows, and the
+        log-probabilities taken (``dops.logprob_rows``) of the adjusted logits -- after
+        penalties and bias, before temperature and the top-k / top-p cut.  bf16 -> f32 is
+        exact and the noise is keyed by (seed, step, token), so a request without
+        penalties draws the same tokens in such a batch as alone.  Still one read-back."""
         ps = [r.params for r in reqs]
         steps = [0 if first else len(r.output) for r in reqs]
-        return dops.sample_rows(logits[:len(reqs)], [p.temperature for p in ps], [p.top_p for p in ps],
-                                [p.top_k for p in ps], [p.seed for p in ps], steps).tolist()
+        if not any(r.special for r in reqs):
+            return dops.sample_rows(logits[:len(reqs)], [p.temperature for p in ps], [p.top_p for p in ps],
+                                    [p.top_k for p in ps], [p.seed for p in ps], steps).tolist()
+        x = logits[:len(reqs)]
+        adj = [p.adjusts for p in ps]
+        want_lp = [p.logprobs is not None for p in ps]
+        if any(adj):
+            x = dops.adjust_logits_rows(
+                x, self._tok_state, [r.slot if a else -1 for r, a in zip(reqs, adj)],
+                [p.presence_penalty for p in ps], [p.frequency_penalty for p in ps],
+                [p.repetition_penalty for p in ps], self._tok_bias)
+        ids = dops.sample_rows(x, [p.temperature for p in ps], [p.top_p for p in ps], [p.top_k for p in ps],
+                               [p.seed for p in ps], steps)
+        if any(p.penalised for p in ps):
+            dops.token_state_update(self._tok_state, [r.slot if p.penalised else -1 for r, p in zip(reqs, ps)], ids)
+        if not any(want_lp):
+            return ids.tolist()
+        chosen, top_ids, top_lp = dops.logprob_rows(x, ids, [p.logprobs if w else -1 for p, w in zip(ps, want_lp)])
+        # one read-back: ids | chosen | top ids | top logprobs as int32 words
+        host = torch.cat([ids.to(torch.int32).view(-1, 1), chosen.view(torch.int32).view(-1, 1), top_ids,
+                          top_lp.view(torch.int32)], 1).cpu()
+        toks = host[:, 0].tolist()
+        lps = host[:, 1].contiguous().view(torch.float32).tolist()
+        tids = host[:, 2:2 + dops.TOP_LOGPROBS_MAX].tolist()
+        tlps = host[:, 2 + dops.TOP_LOGPROBS_MAX:].contiguous().view(torch.float32).tolist()
+        for i, (r, p) in enumerate(zip(reqs, ps)):
+            if want_lp[i]:
+                r.logprobs.append((lps[i], list(zip(tids[i][:p.logprobs], tlps[i][:p.logprobs]))))
+        return toks
+
+    # ------------------------------------------------------------------ prompt scoring
+    SCORE_ROWS = 2048  # logits rows per head GEMM of ``score`` (bounds the [rows, vocab] buffer)
+
+    @torch.no_grad()
+    def _score_now(self, prompts: list[list[int]], top: int = 0) -> list[list]:
+        if self.tp is not None:
+            raise NotImplementedError("prompt scoring is served by single-GPU engines")
+        if not 0 <= top <= dops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"top must be in 0..{dops.TOP_LOGPROBS_MAX}, got {top}")
+        out = []
+        for ids in prompts:
+            if not ids:
+                raise ValueError("empty input")
+            if len(ids) >= self.max_seq:
+                raise ValueError(f"input of {len(ids)} tokens exceeds max_seq {self.max_seq}")
+            t = torch.tensor([ids], dtype=torch.long, device=self.device)
+            h = self.model.hidden_states(t)  # [S, H], final RMSNorm applied (no KV cache touched)
+            parts = []
+            for a in range(0, len(ids) - 1, self.SCORE_ROWS):
+                b = min(len(ids) - 1, a + self.SCORE_ROWS)
+                lp = dops.logprob_rows(self._logits(h[a:b]), t[0, a + 1:b + 1], [top] * (b - a))
+                parts.append(torch.cat([lp[0].view(torch.int32).view(-1, 1), lp[1], lp[2].view(torch.int32)], 1))
+            entries = [None]
+            if parts:
+                host = torch.cat(parts, 0).cpu()
+                lps = host[:, 0].contiguous().view(torch.float32).tolist()
+                tids = host[:, 1:1 + dops.TOP_LOGPROBS_MAX].tolist()
+                tlps = host[:, 1 + dops.TOP_LOGPROBS_MAX:].contiguous().view(torch.float32).tolist()
+                entries += [(lps[i], list(zip(tids[i][:top], tlps[i][:top]))) for i in range(len(lps))]
+            out.append(entries)
+        return out
+
+    def score(self, prompts: list[list[int]], top: int = 0) -> list[list]:
+        """Prompt scoring: for each prompt one entry per position -- None for the first
+        token, then (logprob of token t+1 given tokens <= t, [(id, logprob), ...] of the
+        ``top`` most likely tokens there).  One full forward per prompt (no KV cache
+        touched), the head GEMM and ``logprob_rows`` over chunks of at most ``SCORE_ROWS``
+        rows.  Runs on the engine thread between decode steps like ``embed``."""
+        if self._thread is None:
+            return self._score_now(prompts, top)
+        box, ev = {}, threading.Event()
+
+        def task():
+            try:
+                box["out"] = self._score_now(prompts, top)
+            except Exception as e:  # noqa: BLE001
+                box["err"] = e
+            ev.set()
+
+        with self._cv:
+            self._tasks.append(task)
+            self._cv.notify()
+        ev.wait()
+        if "err" in box:
+            raise box["err"]
+        return box["out"]
 
     def generate(self, prompts: list[list[int]], max_new_tokens: int = 32, temperature: float = 0.0,
-                 top_p: float = 1.0, top_k: int = 0, stop_ids=(), seed: int = 0) -> list[list[int]]:
+                 top_p: float = 1.0, top_k: int = 0, stop_ids=(), seed: int = 0, *, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0, repetition_penalty: float = 1.0, logit_bias: dict | None = None,
+                 logprobs: int | None = None, return_requests: bool = False):
         """Synchronous batched generation (continuous batching when
-        len(prompts) > max_batch)."""
+        len(prompts) > max_batch).  ``return_requests``: the finished ``Request`` objects
+        (``.output``, ``.logprobs``, ``.finish_reason``, ``.error``) instead of the token lists."""
+        reqs = [self.submit(p, SamplingParams(max_new_tokens, temperature, top_p, top_k, tuple(stop_ids), seed,
+                                              presence_penalty, frequency_penalty, repetition_penalty,
+                                              dict(logit_bias) if logit_bias else None, logprobs))
+                for p in prompts]
         if self._thread is not None:
-            reqs = [self.submit(p, SamplingParams(max_new_tokens, temperature, top_p, top_k, tuple(stop_ids), seed))
-                    for p in prompts]
             for r in reqs:
                 r.done.wait()
-            return [r.output for r in reqs]
-        reqs = [self.submit(p, SamplingParams(max_new_tokens, temperature, top_p, top_k, tuple(stop_ids), seed))
-                for p in prompts]
-        while not all(r.done.is_set() for r in reqs):
-            self.step()
-        return [r.output for r in reqs]
+        else:
+            while not all(r.done.is_set() for r in reqs):
+                self.step()
+        return reqs if return_requests else [r.output for r in reqs]
 
     # ------------------------------------------------------------------ background loop (server)
     def start(self):

@@ -51,24 +51,81 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
             if h != f"Bearer {api_key}":
                 raise HTTPException(status_code=401, detail="invalid api key")
 
-    async def run(prompt_ids, body):
-        params = SamplingParams(
-            max_new_tokens=int(body.get("max_tokens") or body.get("max_completion_tokens") or 128),
-            temperature=float(body.get("temperature", 0.0) or 0.0),
-            top_p=float(body.get("top_p", 1.0) or 1.0),
-            top_k=int(body.get("top_k", 0) or 0),
-            stop_ids=_stop_ids(tokenizer, body.get("stop")),
-            seed=int(body.get("seed", 0) or 0),
-        )
+    def sampling_params(body, chat: bool) -> SamplingParams:
+        """The request body's sampling fields (both routes, streaming or not).  Raises
+        ValueError on a bad value (answered with HTTP 400)."""
+        try:
+            if chat:
+                lp = body.get("logprobs")
+                if lp not in (None, True, False):
+                    raise ValueError("logprobs must be a boolean on /chat/completions")
+                top = body.get("top_logprobs")
+                if top is not None and not lp:
+                    raise ValueError("top_logprobs needs logprobs: true")
+                logprobs = (0 if top is None else top) if lp else None
+            else:
+                logprobs = body.get("logprobs")
+            if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int)):
+                raise ValueError(f"logprobs / top_logprobs must be an integer in 0..20, got {logprobs!r}")
+            bias = body.get("logit_bias")
+            if bias is not None and not isinstance(bias, dict):
+                raise ValueError("logit_bias must be an object of token id -> bias")
+            return SamplingParams(
+                max_new_tokens=int(body.get("max_tokens") or body.get("max_completion_tokens") or 128),
+                temperature=float(body.get("temperature", 0.0) or 0.0),
+                top_p=float(body.get("top_p", 1.0) or 1.0),
+                top_k=int(body.get("top_k", 0) or 0),
+                stop_ids=_stop_ids(tokenizer, body.get("stop")),
+                seed=int(body.get("seed", 0) or 0),
+                presence_penalty=float(body.get("presence_penalty") or 0.0),
+                frequency_penalty=float(body.get("frequency_penalty") or 0.0),
+                repetition_penalty=float(1.0 if body.get("repetition_penalty") is None
+                                         else body["repetition_penalty"]),
+                logit_bias=bias or None,
+                logprobs=logprobs,
+            )
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+
+    def bad_request(e):
+        return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
+
+    async def run(prompt_ids, params):
         r = engine.submit(prompt_ids, params)
         while not r.done.is_set():
             await asyncio.sleep(0.002)
         if r.error:
             stats["errors"] += 1
+            if "logit_bias" in r.error:  # rejected at admission: the caller's mistake
+                raise ValueError(r.error)
             raise HTTPException(status_code=500, detail=r.error)
         stats["prompt_tokens"] += len(prompt_ids)
         stats["completion_tokens"] += len(r.output)
         return r
+
+    def tok_str(t: int) -> str:
+        return tokenizer.decode([t])
+
+    def chat_logprobs(toks, entries):
+        """OpenAI chat shape: one entry per token with its top list."""
+        def one(t, lp):
+            s_ = tok_str(t)
+            return {"token": s_, "logprob": lp, "bytes": list(s_.encode("utf-8"))}
+
+        return {"content": [dict(one(t, e[0]), top_logprobs=[one(i, l) for i, l in e[1]])
+                            for t, e in zip(toks, entries)]}
+
+    def text_logprobs(toks, entries, offset: int = 0):
+        """OpenAI completions shape; ``entries`` may start with None (the first prompt token)."""
+        out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+        for t, e in zip(toks, entries):
+            s_ = tok_str(t)
+            out["tokens"].append(s_)
+            out["token_logprobs"].append(None if e is None else e[0])
+            out["top_logprobs"].append(None if e is None else {tok_str(i): l for i, l in e[1]})
+            out["text_offset"].append(offset)
+            offset += len(s_)
+        return out
 
     def usage(r):
         return {"prompt_tokens": len(r.prompt), "completion_tokens": len(r.output),
@@ -106,16 +163,20 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
         stats["requests"] += 1
         msgs = body.get("messages") or []
         ids = tokenizer.apply_chat_template(msgs)
-        if body.get("stream"):
-            return StreamingResponse(_stream(ids, body, chat=True), media_type="text/event-stream")
-        r = await run(ids, body)
+        try:
+            params = sampling_params(body, chat=True)
+            if body.get("stream"):
+                return StreamingResponse(_stream(ids, params, chat=True), media_type="text/event-stream")
+            r = await run(ids, params)
+        except ValueError as e:
+            return bad_request(e)
         text = tokenizer.decode([t for t in r.output if t not in engine.eos_ids])
+        choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": r.finish_reason}
+        if params.logprobs is not None:
+            choice["logprobs"] = chat_logprobs(r.output, r.logprobs)
         return JSONResponse({
             "id": f"chatcmpl-{uuid.uuid4().hex[:24]}", "object": "chat.completion", "created": int(time.time()),
-            "model": body.get("model", model_name),
-            "choices": [{"index": 0, "message": {"role": "assistant", "content": text},
-                         "finish_reason": r.finish_reason}],
-            "usage": usage(r)})
+            "model": body.get("model", model_name), "choices": [choice], "usage": usage(r)})
 
     @app.post("/v1/completions")
     @app.post("/completions")
@@ -124,15 +185,36 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
         body = await req.json()
         stats["requests"] += 1
         prompt = body.get("prompt", "")
-        ids = tokenizer.encode(prompt if isinstance(prompt, str) else prompt[0])
-        if body.get("stream"):
-            return StreamingResponse(_stream(ids, body, chat=False), media_type="text/event-stream")
-        r = await run(ids, body)
-        text = tokenizer.decode([t for t in r.output if t not in engine.eos_ids])
+        prompt = prompt if isinstance(prompt, str) else prompt[0]
+        ids = tokenizer.encode(prompt)
+        echo = bool(body.get("echo"))
+        try:
+            params = sampling_params(body, chat=False)
+            if body.get("stream"):
+                return StreamingResponse(_stream(ids, params, chat=False), media_type="text/event-stream")
+            scored = None
+            if echo and params.logprobs is not None:  # prompt scoring: one full forward, no KV cache
+                scored = (await asyncio.get_running_loop().run_in_executor(
+                    None, engine.score, [ids], params.logprobs))[0]
+            if echo and body.get("max_tokens") == 0:  # nothing generated
+                out, out_lp, reason = [], [], "length"
+                use = {"prompt_tokens": len(ids), "completion_tokens": 0, "total_tokens": len(ids)}
+                stats["prompt_tokens"] += len(ids)
+            else:
+                r = await run(ids, params)
+                out, out_lp, reason, use = r.output, r.logprobs, r.finish_reason, usage(r)
+        except (ValueError, NotImplementedError) as e:
+            return bad_request(e)
+        text = tokenizer.decode([t for t in out if t not in engine.eos_ids])
+        choice = {"index": 0, "text": (prompt + text) if echo else text, "finish_reason": reason}
+        if params.logprobs is not None:
+            if scored is not None:
+                choice["logprobs"] = text_logprobs(list(ids) + list(out), scored + list(out_lp))
+            else:
+                choice["logprobs"] = text_logprobs(out, out_lp, len(prompt) if echo else 0)
         return JSONResponse({
             "id": f"cmpl-{uuid.uuid4().hex[:24]}", "object": "text_completion", "created": int(time.time()),
-            "model": body.get("model", model_name),
-            "choices": [{"index": 0, "text": text, "finish_reason": r.finish_reason}], "usage": usage(r)})
+            "model": body.get("model", model_name), "choices": [choice], "usage": use})
 
     @app.post("/v1/embeddings")
     @app.post("/embeddings")
@@ -165,26 +247,25 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
             "data": [{"object": "embedding", "index": i, "embedding": v.tolist()} for i, v in enumerate(vec)],
             "usage": {"prompt_tokens": n, "total_tokens": n}})
 
-    async def _stream(ids, body, chat: bool):
-        r = engine.submit(ids, SamplingParams(
-            max_new_tokens=int(body.get("max_tokens") or body.get("max_completion_tokens") or 128),
-            temperature=float(body.get("temperature", 0.0) or 0.0), top_p=float(body.get("top_p", 1.0) or 1.0),
-            top_k=int(body.get("top_k", 0) or 0), stop_ids=_stop_ids(tokenizer, body.get("stop")),
-            seed=int(body.get("seed", 0) or 0)))
+    async def _stream(ids, params, chat: bool):
+        r = engine.submit(ids, params)
         sent = 0
         cid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         while True:
             done = r.done.is_set()
             toks = r.output[sent:]
             if toks:
-                sent += len(toks)
                 text = tokenizer.decode([t for t in toks if t not in engine.eos_ids])
                 if chat:
-                    chunk = {"id": cid, "object": "chat.completion.chunk", "model": model_name,
-                             "choices": [{"index": 0, "delta": {"content": text}, "finish_reason": None}]}
+                    choice = {"index": 0, "delta": {"content": text}, "finish_reason": None}
                 else:
-                    chunk = {"id": cid, "object": "text_completion", "model": model_name,
-                             "choices": [{"index": 0, "text": text, "finish_reason": None}]}
+                    choice = {"index": 0, "text": text, "finish_reason": None}
+                if params.logprobs is not None:  # the entries of this chunk's tokens
+                    ent = r.logprobs[sent:sent + len(toks)]
+                    choice["logprobs"] = chat_logprobs(toks, ent) if chat else text_logprobs(toks, ent)
+                sent += len(toks)
+                chunk = {"id": cid, "object": "chat.completion.chunk" if chat else "text_completion",
+                         "model": model_name, "choices": [choice]}
                 yield f"data: {json.dumps(chunk)}\n\n"
             if done and sent >= len(r.output):
                 break
