@@ -87,6 +87,28 @@ ATTN_DV = (ULP_F32, 0.00408)  # 2 x 0 < one ulp; 2 x 0.00204
 ATTN_ROPE_DQKV_MEASURED = (0.00389, 0.00101)
 ATTN_ROPE_DQKV = (ULP_BF16, 0.00202)  # 2 x 0.00389 < one ulp; 2 x 0.00101
 
+# Decode attention (tests/test_decode_exact_gpu.py; ``python -m tests.test_decode_exact_gpu`` prints the
+# measurements): the fp32 model of the algorithm documented in decode.hip (online softmax in the exp2
+# domain per 64-key wave, the waves and then the 256-key splits merged, one division) against an fp64
+# softmax; each head's output against its own maximum.  _MFMA: head_dim 128, P rounded to bf16 before the
+# PV product (the abs term is that rounding's); _F32: the scalar kernel (head_dim 64 / 32) and the split
+# merge of decode_fuse.h, P and the partials in fp32.
+DECODE_O_MFMA_MEASURED = (0.00383, 0.00183)
+DECODE_O_MFMA = (ULP_BF16, 0.00366)  # 2 x 0.00383 < one ulp; 2 x 0.00183
+DECODE_O_F32_MEASURED = (0.00389, 5.9e-07)
+DECODE_O_F32 = (ULP_BF16, 1.18e-06)  # 2 x 0.00389 < one ulp; 2 x 5.9e-07
+# Decode GEMMs (tests/test_skinny_exact_gpu.py; ``python -m tests.test_skinny_exact_gpu`` prints the
+# measurements): fp32 ``x.float() @ w.float().t()`` against the fp64 product at the Gaussian inputs of the
+# tests, each output against its row's maximum.  W8_Y: the weights are the reference decode of the e4m3
+# codes, the channel scale included.  W8_DEQ_Y: w8_linear's fallback (shapes the decode kernel does not take)
+# dequantises to bf16 first -- its weights are the bf16 rounding of code * scale, the reference's too.
+SKINNY_Y_MEASURED = (0.00388, 2.74e-07)
+SKINNY_Y = (ULP_BF16, 5.48e-07)  # 2 x 0.00388 < one ulp; 2 x 2.74e-07
+W8_Y_MEASURED = (0.00388, 7.83e-07)
+W8_Y = (ULP_BF16, 1.57e-06)  # 2 x 0.00388 < one ulp; 2 x 7.83e-07
+W8_DEQ_Y_MEASURED = (0.00379, 2.6e-07)
+W8_DEQ_Y = (ULP_BF16, 5.2e-07)  # 2 x 0.00379 < one ulp; 2 x 2.6e-07
+
 
 def assert_exact(out: torch.Tensor, want: torch.Tensor, name: str = "") -> None:
     """Assert ``torch.equal(out, want)``: same shape, same dtype, every element equal (no tolerance).
