@@ -165,226 +165,196 @@ at::Tensor transpose2d(const at::Tensor& in, const c10::optional<at::Tensor>& sc
   return out;
 }
 
-// out[M, N] = beta * out + alpha * op(a) op(b) on the 8-phase MFMA GEMM (csrc/kernels/gemm8.hip).
-// a: [M, K] when a_kc (k-contiguous) else [K, M]; b: [N, K] when b_kc else [K, N]; all row-strided
-// bf16 views, out fp32 or bf16; alpha = alpha_f * (the optional f32 device scalar alpha_t).
-// Returns false (nothing launched) for shapes the kernel does not take.
-bool gemm8(const at::Tensor& a, bool a_kc, const at::Tensor& b, bool b_kc, at::Tensor& out, double beta,
-           const c10::optional<at::Tensor>& alpha_t, double alpha_f, int64_t ph) {
-  MX_CHECK(a.is_cuda() && b.is_cuda() && out.is_cuda(), "gemm8: GPU tensors");
-  MX_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16, "gemm8: bf16 operands");
-  MX_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == at::kBFloat16, "gemm8: fp32 / bf16 output");
-  MX_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 2, "gemm8: 2-D operands");
+// ---------------------------------------------------------------- gemm8 (csrc/kernels/gemm8.hip)
+// The seven gemm8 ops share their argument handling: the helpers below check the tensors and fill the
+// launch description (kernels/gemm8_args.h) that the launcher is then called from.  Every op returns
+// false when nothing was launched: a layout the helpers do not take, or the launcher's -1
+// (mx::g8_takes, the one operand check).
+
+inline const uint16_t* g8p(const mx::G8Mat& m) { return static_cast<const uint16_t*>(m.p); }
+inline uint16_t* g8pm(const mx::G8Mat& m) { return static_cast<uint16_t*>(const_cast<void*>(m.p)); }
+
+// optional 1-element f32 scalar on `dev` -> its device pointer (nullptr when absent)
+const float* f32_scalar(const char* what, const c10::optional<at::Tensor>& t, const at::Device& dev) {
+  if (!t.has_value()) return nullptr;
+  MX_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1 && t->device() == dev, what,
+           ": f32 scalar on the device");
+  return t->data_ptr<float>();
+}
+
+// Operands a [M, K] (a_kc) / [K, M] and b [N, K] (b_kc) / [K, N], row-strided bf16 views, and -- when
+// given -- the output [M, N] (bf16, or fp32 with f32_ok) into L.A / L.B / L.C, M, N, K, out_f32.
+// False: a layout no launcher takes (an inner stride, a dimension past int).
+bool g8_fill(const char* op, mx::G8Launch& L, const at::Tensor& a, bool a_kc, const at::Tensor& b, bool b_kc,
+             const at::Tensor* out, bool f32_ok) {
+  MX_CHECK(a.is_cuda() && b.is_cuda() && (!out || out->is_cuda()), op, ": GPU tensors");
+  MX_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16, op, ": bf16 operands");
+  MX_CHECK(!out || out->scalar_type() == at::kBFloat16 || (f32_ok && out->scalar_type() == at::kFloat), op,
+           f32_ok ? ": fp32 / bf16 output" : ": bf16 output");
+  MX_CHECK(a.dim() == 2 && b.dim() == 2 && (!out || out->dim() == 2), op, ": 2-D operands");
   const int64_t M = a_kc ? a.size(0) : a.size(1), K = a_kc ? a.size(1) : a.size(0);
   const int64_t N = b_kc ? b.size(0) : b.size(1), Kb = b_kc ? b.size(1) : b.size(0);
-  MX_CHECK(K == Kb && out.size(0) == M && out.size(1) == N, "gemm8: shape mismatch");
-  if (a.stride(1) != 1 || b.stride(1) != 1 || out.stride(1) != 1) return false;
+  MX_CHECK(K == Kb && (!out || (out->size(0) == M && out->size(1) == N)), op, ": shape mismatch");
+  if (a.stride(1) != 1 || b.stride(1) != 1 || (out && out->stride(1) != 1)) return false;
   if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return false;
-  const float* sc = nullptr;
-  if (alpha_t.has_value()) {
-    MX_CHECK(alpha_t->scalar_type() == at::kFloat && alpha_t->numel() == 1 && alpha_t->device() == a.device(),
-             "gemm8 alpha_t: f32 scalar on the device");
-    sc = alpha_t->data_ptr<float>();
-  }
-  DevGuard g(a.device());
-  const int rc = mx_gemm8(bf(a), a.stride(0), a_kc ? 1 : 0, bf(b), b.stride(0), b_kc ? 1 : 0, out.data_ptr(),
-                          out.stride(0), out.scalar_type() == at::kFloat ? 1 : 0, (int)M, (int)N, (int)K, (float)beta,
-                          sc, (float)alpha_f, (int)ph, cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
+  L.A = {a.data_ptr(), a.stride(0), a_kc ? 1 : 0};
+  L.B = {b.data_ptr(), b.stride(0), b_kc ? 1 : 0};
+  if (out) L.C = {out->data_ptr(), out->stride(0), 1};
+  L.out_f32 = out && out->scalar_type() == at::kFloat ? 1 : 0;
+  L.M = (int)M, L.N = (int)N, L.K = (int)K;
   return true;
+}
+
+// The RoPE epilogue block of gemm8_rope / gemm8_rope_tail: x [B*S, K] (row-strided), w [(Hq + 2 Hkv) *
+// 128, K] -> q [B, Hq, S, 128], k / v [B, Hkv, S, 128] (preallocated, contiguous), rotated with the f32
+// tables cos / sin [>= S, 64] at positions 0..S-1.  Fills the operands and L.ep.
+bool g8_fill_rope(const char* op, mx::G8Launch& L, const at::Tensor& x, const at::Tensor& w, const at::Tensor& cos,
+                  const at::Tensor& sin, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, at::Tensor& q, at::Tensor& k,
+                  at::Tensor& v) {
+  MX_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(0) == B * S, op, ": shapes");
+  MX_CHECK(w.size(0) == (Hq + 2 * Hkv) * 128, op, ": head dim 128");
+  MX_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+               sin.is_contiguous() && cos.size(-1) == 64 && cos.size(0) >= S && sin.sizes() == cos.sizes(),
+           op, ": f32 [>= S, 64] tables");
+  for (const at::Tensor* t : {&q, &k, &v})
+    MX_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(), op, ": bf16 outputs");
+  MX_CHECK(q.numel() == B * Hq * S * 128 && k.numel() == B * Hkv * S * 128 && v.numel() == k.numel(), op,
+           ": output sizes");
+  if (!g8_fill(op, L, x, true, w, true, nullptr, false)) return false;
+  L.epi = mx::G8_EPI_ROPE;
+  L.ep.q = bfm(q), L.ep.k = bfm(k), L.ep.v = bfm(v);
+  L.ep.cosb = cos.data_ptr<float>(), L.ep.sinb = sin.data_ptr<float>();
+  L.ep.S = (int)S, L.ep.Hq = (int)Hq, L.ep.Hkv = (int)Hkv;
+  return true;
+}
+
+// a launcher's return code -> the op's: false for -1 (nothing launched), an error for a HIP failure
+bool g8_launched(const char* op, int rc) {
+  if (rc == -1) return false;
+  TORCH_CHECK(rc == 0, "mxllm kernel launch failed (", op, ") rc=", rc, " ", hipGetErrorString((hipError_t)(rc > 0 ? rc : 1)));
+  return true;
+}
+
+// out[M, N] = beta * out + alpha * op(a) op(b); out fp32 or bf16; alpha = alpha_f * (the optional f32
+// device scalar alpha_t).
+bool gemm8(const at::Tensor& a, bool a_kc, const at::Tensor& b, bool b_kc, at::Tensor& out, double beta,
+           const c10::optional<at::Tensor>& alpha_t, double alpha_f, int64_t ph) {
+  mx::G8Launch L{};
+  if (!g8_fill("gemm8", L, a, a_kc, b, b_kc, &out, true)) return false;
+  const float* sc = f32_scalar("gemm8 alpha_t", alpha_t, a.device());
+  DevGuard g(a.device());
+  return g8_launched("mx_gemm8", mx_gemm8(g8p(L.A), L.A.ld, L.A.kc, g8p(L.B), L.B.ld, L.B.kc, out.data_ptr(), L.C.ld,
+                                          L.out_f32, L.M, L.N, L.K, (float)beta, sc, (float)alpha_f, (int)ph,
+                                          cur_stream()));
 }
 
 // out[M, N] (bf16, beta 0) = alpha op(a) op(b) that also writes one fp32 sum of squares of the stored
 // values per 256 x 256 output tile into sq (>= (M / 256) * (N / 256) elements, row-major tile order):
-// the gradient-clip norm's partials straight from the weight-gradient GEMMs.  False: nothing launched.
+// the gradient-clip norm's partials straight from the weight-gradient GEMMs.
 bool gemm8_sq(const at::Tensor& a, bool a_kc, const at::Tensor& b, bool b_kc, at::Tensor& out, at::Tensor& sq,
               const c10::optional<at::Tensor>& alpha_t, double alpha_f) {
-  MX_CHECK(a.is_cuda() && b.is_cuda() && out.is_cuda() && sq.is_cuda(), "gemm8_sq: GPU tensors");
-  MX_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16 &&
-               out.scalar_type() == at::kBFloat16 && sq.scalar_type() == at::kFloat,
-           "gemm8_sq: bf16 operands and output, f32 partials");
-  MX_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 2, "gemm8_sq: 2-D operands");
-  const int64_t M = a_kc ? a.size(0) : a.size(1), K = a_kc ? a.size(1) : a.size(0);
-  const int64_t N = b_kc ? b.size(0) : b.size(1), Kb = b_kc ? b.size(1) : b.size(0);
-  MX_CHECK(K == Kb && out.size(0) == M && out.size(1) == N, "gemm8_sq: shape mismatch");
-  if (a.stride(1) != 1 || b.stride(1) != 1 || out.stride(1) != 1 || !sq.is_contiguous()) return false;
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || M % 256 || N % 256) return false;
-  MX_CHECK(sq.numel() >= (M / 256) * (N / 256), "gemm8_sq: partials buffer too small");
-  const float* sc = nullptr;
-  if (alpha_t.has_value()) {
-    MX_CHECK(alpha_t->scalar_type() == at::kFloat && alpha_t->numel() == 1 && alpha_t->device() == a.device(),
-             "gemm8_sq alpha_t: f32 scalar on the device");
-    sc = alpha_t->data_ptr<float>();
-  }
+  MX_CHECK(sq.is_cuda() && sq.scalar_type() == at::kFloat, "gemm8_sq: f32 GPU partials");
+  mx::G8Launch L{};
+  if (!g8_fill("gemm8_sq", L, a, a_kc, b, b_kc, &out, false) || !sq.is_contiguous()) return false;
+  if (L.M % 256 || L.N % 256) return false;
+  MX_CHECK(sq.numel() >= (int64_t)(L.M / 256) * (L.N / 256), "gemm8_sq: partials buffer too small");
+  const float* sc = f32_scalar("gemm8_sq alpha_t", alpha_t, a.device());
   DevGuard g(a.device());
-  const int rc = mx_gemm8_sq(bf(a), a.stride(0), a_kc ? 1 : 0, bf(b), b.stride(0), b_kc ? 1 : 0, bfm(out),
-                             out.stride(0), (int)M, (int)N, (int)K, sc, (float)alpha_f, sq.data_ptr<float>(),
-                             cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  return g8_launched("mx_gemm8_sq", mx_gemm8_sq(g8p(L.A), L.A.ld, L.A.kc, g8p(L.B), L.B.ld, L.B.kc, g8pm(L.C), L.C.ld,
+                                                L.M, L.N, L.K, sc, (float)alpha_f, sq.data_ptr<float>(),
+                                                cur_stream()));
 }
 
 // out[M, N] (bf16) = op(a) op(b) with the tail-balanced launch (mx_gemm8_tail): the output split at
 // `at` columns (rows when `rows`) -- whole waves of tiles before it, half-K workgroups summed through
-// an fp32 workspace after it.  Returns false (nothing launched) for shapes it does not take.
+// an fp32 workspace after it.  sq: one sum of squares per 256 x 256 tile (plain part's tiles, then the
+// split part's).
 bool gemm8_tail(const at::Tensor& a, bool a_kc, const at::Tensor& b, bool b_kc, at::Tensor& out, int64_t at,
                 bool rows, int64_t ph, const c10::optional<at::Tensor>& sq) {
-  MX_CHECK(a.is_cuda() && b.is_cuda() && out.is_cuda(), "gemm8_tail: GPU tensors");
-  MX_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
-           "gemm8_tail: bf16 operands and output");
-  MX_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 2, "gemm8_tail: 2-D operands");
-  const int64_t M = a_kc ? a.size(0) : a.size(1), K = a_kc ? a.size(1) : a.size(0);
-  const int64_t N = b_kc ? b.size(0) : b.size(1), Kb = b_kc ? b.size(1) : b.size(0);
-  MX_CHECK(K == Kb && out.size(0) == M && out.size(1) == N, "gemm8_tail: shape mismatch");
-  const int64_t lim = rows ? M : N;
-  if (a.stride(1) != 1 || b.stride(1) != 1 || out.stride(1) != 1 || at <= 0 || at >= lim) return false;
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return false;
+  mx::G8Launch L{};
+  if (!g8_fill("gemm8_tail", L, a, a_kc, b, b_kc, &out, false)) return false;
+  const int64_t lim = rows ? L.M : L.N;
+  if (at <= 0 || at >= lim) return false;
   float* sqp = nullptr;
-  if (sq.has_value()) {  // one sum of squares per 256 x 256 tile (plain part's tiles, then the split part's)
+  if (sq.has_value()) {
     MX_CHECK(sq->scalar_type() == at::kFloat && sq->is_contiguous() && sq->device() == a.device(),
              "gemm8_tail sq: contiguous f32 on the device");
-    if (M % 256 || N % 256) return false;
-    MX_CHECK(sq->numel() >= (M / 256) * (N / 256), "gemm8_tail sq: partials buffer too small");
+    if (L.M % 256 || L.N % 256) return false;
+    MX_CHECK(sq->numel() >= (int64_t)(L.M / 256) * (L.N / 256), "gemm8_tail sq: partials buffer too small");
     sqp = sq->data_ptr<float>();
   }
   DevGuard g(a.device());
-  auto ws = at::empty({2 * (lim - at) * (rows ? N : M)}, a.options().dtype(at::kFloat));
-  const int rc = mx_gemm8_tail(bf(a), a.stride(0), a_kc ? 1 : 0, bf(b), b.stride(0), b_kc ? 1 : 0, bfm(out),
-                               out.stride(0), (int)M, (int)N, (int)K, rows ? 1 : 0, (int)at, ws.data_ptr<float>(),
-                               (int)ph, cur_stream(), sqp);
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  auto ws = at::empty({2 * (lim - at) * (rows ? L.N : L.M)}, a.options().dtype(at::kFloat));
+  return g8_launched("mx_gemm8_tail",
+                     mx_gemm8_tail(g8p(L.A), L.A.ld, L.A.kc, g8p(L.B), L.B.ld, L.B.kc, g8pm(L.C), L.C.ld, L.M, L.N, L.K,
+                                   rows ? 1 : 0, (int)at, ws.data_ptr<float>(), (int)ph, cur_stream(), sqp));
 }
 
-// Forward qkv projection with RoPE and the head split in the GEMM epilogue (gemm8 G8_EPI_ROPE):
-// x [B*S, K] (row-strided), w [(Hq + 2 Hkv) * 128, K] -> q [B, Hq, S, 128], k / v [B, Hkv, S, 128]
-// (preallocated, contiguous), rotated with the f32 tables cos / sin [>= S, 64] at positions 0..S-1.
-// Returns false (nothing launched) for shapes the kernel does not take.
+// Forward qkv projection with RoPE and the head split in the GEMM epilogue (G8_EPI_ROPE; g8_fill_rope).
 bool gemm8_rope(const at::Tensor& x, const at::Tensor& w, const at::Tensor& cos, const at::Tensor& sin, int64_t B,
                 int64_t S, int64_t Hq, int64_t Hkv, at::Tensor& q, at::Tensor& k, at::Tensor& v) {
-  MX_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
-           "gemm8_rope: bf16 GPU operands");
-  MX_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) && x.size(0) == B * S, "gemm8_rope: shapes");
-  MX_CHECK(w.size(0) == (Hq + 2 * Hkv) * 128, "gemm8_rope: head dim 128");
-  MX_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(-1) == 64 && cos.size(0) >= S && sin.sizes() == cos.sizes(),
-           "gemm8_rope: f32 [>= S, 64] tables");
-  for (const at::Tensor* t : {&q, &k, &v})
-    MX_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(), "gemm8_rope: bf16 outputs");
-  MX_CHECK(q.numel() == B * Hq * S * 128 && k.numel() == B * Hkv * S * 128 && v.numel() == k.numel(),
-           "gemm8_rope: output sizes");
-  if (x.stride(1) != 1 || w.stride(1) != 1) return false;
+  mx::G8Launch L{};
+  if (!g8_fill_rope("gemm8_rope", L, x, w, cos, sin, B, S, Hq, Hkv, q, k, v)) return false;
   DevGuard g(x.device());
-  MxG8Epi ep{};
-  ep.q = bfm(q);
-  ep.k = bfm(k);
-  ep.v = bfm(v);
-  ep.cosb = cos.data_ptr<float>();
-  ep.sinb = sin.data_ptr<float>();
-  ep.S = (int)S;
-  ep.Hq = (int)Hq;
-  ep.Hkv = (int)Hkv;
-  const int rc = mx_gemm8_epi(bf(x), x.stride(0), bf(w), w.stride(0), nullptr, 0, (int)x.size(0), (int)w.size(0),
-                              (int)x.size(1), 1, ep, cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  return g8_launched("mx_gemm8_epi", mx_gemm8_epi(g8p(L.A), L.A.ld, g8p(L.B), L.B.ld, nullptr, 0, L.M, L.N, L.K,
+                                                  mx::G8_EPI_ROPE, L.ep, cur_stream()));
 }
 
 // gemm8_rope on the tail-balanced schedule (mx_gemm8_rope_tail): columns [0, at) through the RoPE
 // epilogue, the rest as half-K images summed, rotated and scattered by one pass -- bitwise
-// gemm8_tail(at) followed by rope_split.  Returns false (nothing launched) for shapes it does not take.
+// gemm8_tail(at) followed by rope_split.
 bool gemm8_rope_tail(const at::Tensor& x, const at::Tensor& w, const at::Tensor& cos, const at::Tensor& sin, int64_t B,
                      int64_t S, int64_t Hq, int64_t Hkv, at::Tensor& q, at::Tensor& k, at::Tensor& v, int64_t at) {
-  MX_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
-           "gemm8_rope_tail: bf16 GPU operands");
-  MX_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) && x.size(0) == B * S, "gemm8_rope_tail: shapes");
-  MX_CHECK(w.size(0) == (Hq + 2 * Hkv) * 128, "gemm8_rope_tail: head dim 128");
-  MX_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(-1) == 64 && cos.size(0) >= S && sin.sizes() == cos.sizes(),
-           "gemm8_rope_tail: f32 [>= S, 64] tables");
-  for (const at::Tensor* t : {&q, &k, &v})
-    MX_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(), "gemm8_rope_tail: bf16 outputs");
-  MX_CHECK(q.numel() == B * Hq * S * 128 && k.numel() == B * Hkv * S * 128 && v.numel() == k.numel(),
-           "gemm8_rope_tail: output sizes");
-  if (x.stride(1) != 1 || w.stride(1) != 1 || at <= 0 || at >= w.size(0)) return false;
-  if (x.size(0) > INT32_MAX || x.size(1) > INT32_MAX) return false;
+  mx::G8Launch L{};
+  if (!g8_fill_rope("gemm8_rope_tail", L, x, w, cos, sin, B, S, Hq, Hkv, q, k, v) || at <= 0 || at >= L.N) return false;
   DevGuard g(x.device());
-  auto ws = at::empty({2 * x.size(0) * (w.size(0) - at)}, x.options().dtype(at::kFloat));
-  MxG8Epi ep{};
-  ep.q = bfm(q);
-  ep.k = bfm(k);
-  ep.v = bfm(v);
-  ep.cosb = cos.data_ptr<float>();
-  ep.sinb = sin.data_ptr<float>();
-  ep.S = (int)S;
-  ep.Hq = (int)Hq;
-  ep.Hkv = (int)Hkv;
-  const int rc = mx_gemm8_rope_tail(bf(x), x.stride(0), bf(w), w.stride(0), (int)x.size(0), (int)w.size(0),
-                                    (int)x.size(1), (int)at, ws.data_ptr<float>(), ep, cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  auto ws = at::empty({2 * (int64_t)L.M * (L.N - at)}, x.options().dtype(at::kFloat));
+  return g8_launched("mx_gemm8_rope_tail", mx_gemm8_rope_tail(g8p(L.A), L.A.ld, g8p(L.B), L.B.ld, L.M, L.N, L.K, (int)at,
+                                                              ws.data_ptr<float>(), L.ep, cur_stream()));
 }
 
-// Forward gate-up projection with SwiGLU in the GEMM epilogue (gemm8 G8_EPI_SWIGLU): x [T, K],
+// Forward gate-up projection with SwiGLU in the GEMM epilogue (G8_EPI_SWIGLU): x [T, K],
 // w = [gate; up] [2F, K] -> gu [T, 2F] (the projection output, kept for the backward) and
-// m = silu(gate) * up [T, F].  Returns false (nothing launched) for shapes the kernel does not take.
+// m = silu(gate) * up [T, F].
 bool gemm8_swiglu(const at::Tensor& x, const at::Tensor& w, at::Tensor& gu, at::Tensor& m) {
-  MX_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
-               gu.scalar_type() == at::kBFloat16 && m.scalar_type() == at::kBFloat16,
-           "gemm8_swiglu: bf16 GPU tensors");
-  MX_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) && gu.size(0) == x.size(0) &&
-               gu.size(1) == w.size(0) && m.size(0) == x.size(0) && 2 * m.size(1) == w.size(0),
-           "gemm8_swiglu: shapes");
-  if (x.stride(1) != 1 || w.stride(1) != 1 || gu.stride(1) != 1 || m.stride(1) != 1) return false;
+  mx::G8Launch L{};
+  const bool ok = g8_fill("gemm8_swiglu", L, x, true, w, true, &gu, false);
+  MX_CHECK(m.scalar_type() == at::kBFloat16 && m.dim() == 2 && m.size(0) == x.size(0) && 2 * m.size(1) == w.size(0),
+           "gemm8_swiglu: m [T, F] bf16");
+  if (!ok || m.stride(1) != 1) return false;
   DevGuard g(x.device());
-  MxG8Epi ep{};
-  ep.m = bfm(m);
-  ep.ldm = m.stride(0);
-  const int rc = mx_gemm8_epi(bf(x), x.stride(0), bf(w), w.stride(0), bfm(gu), gu.stride(0), (int)x.size(0),
-                              (int)w.size(0), (int)x.size(1), 2, ep, cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  L.ep.m = bfm(m);
+  L.ep.ldm = m.stride(0);
+  return g8_launched("mx_gemm8_epi", mx_gemm8_epi(g8p(L.A), L.A.ld, g8p(L.B), L.B.ld, g8pm(L.C), L.C.ld, L.M, L.N, L.K,
+                                                  mx::G8_EPI_SWIGLU, L.ep, cur_stream()));
 }
 
-// The down projection's dX GEMM with the SwiGLU backward in its epilogue (gemm8 G8_EPI_SWIGLU_BWD):
+// The down projection's dX GEMM with the SwiGLU backward in its epilogue (G8_EPI_SWIGLU_BWD):
 // dy [T, H] and w = W_down [H, F] -> dgu [T, 2F] from the forward's gu [T, 2F] (dm never reaches
-// HBM), and with m given also m = silu(g) u [T, F] (the recompute path's dW input).  Returns false
-// (nothing launched) for shapes the kernel does not take.
+// HBM), and with m given also m = silu(g) u [T, F] (the recompute path's dW input).
 bool gemm8_swiglu_bwd(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& gu, at::Tensor& dgu,
                       const c10::optional<at::Tensor>& m) {
-  MX_CHECK(dy.is_cuda() && w.is_cuda() && gu.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
-               w.scalar_type() == at::kBFloat16 && gu.scalar_type() == at::kBFloat16 &&
-               dgu.scalar_type() == at::kBFloat16,
+  mx::G8Launch L{};
+  const bool ok = g8_fill("gemm8_swiglu_bwd", L, dy, true, w, false, nullptr, false);
+  MX_CHECK(gu.is_cuda() && gu.scalar_type() == at::kBFloat16 && dgu.scalar_type() == at::kBFloat16,
            "gemm8_swiglu_bwd: bf16 GPU tensors");
-  MX_CHECK(dy.dim() == 2 && w.dim() == 2 && gu.dim() == 2 && dgu.dim() == 2 && dy.size(1) == w.size(0) &&
-               gu.size(0) == dy.size(0) && gu.size(1) == 2 * w.size(1) && dgu.sizes() == gu.sizes(),
+  MX_CHECK(gu.dim() == 2 && dgu.dim() == 2 && gu.size(0) == dy.size(0) && gu.size(1) == 2 * w.size(1) &&
+               dgu.sizes() == gu.sizes(),
            "gemm8_swiglu_bwd: shapes");
   if (m) {
     MX_CHECK(m->scalar_type() == at::kBFloat16 && m->dim() == 2 && m->size(0) == dy.size(0) &&
                  m->size(1) == w.size(1),
              "gemm8_swiglu_bwd: m [T, F] bf16");
     if (m->stride(1) != 1) return false;
+    L.ep.m = reinterpret_cast<uint16_t*>(m->data_ptr());
+    L.ep.ldm = m->stride(0);
   }
-  if (dy.stride(1) != 1 || w.stride(1) != 1 || gu.stride(1) != 1 || dgu.stride(1) != 1) return false;
+  if (!ok || gu.stride(1) != 1 || dgu.stride(1) != 1) return false;
   DevGuard g(dy.device());
-  MxG8Epi ep{};
-  ep.gu = bf(gu);
-  ep.ldg = gu.stride(0);
-  if (m) {
-    ep.m = reinterpret_cast<uint16_t*>(m->data_ptr());
-    ep.ldm = m->stride(0);
-  }
-  const int rc = mx_gemm8_epi(bf(dy), dy.stride(0), bf(w), w.stride(0), bfm(dgu), dgu.stride(0), (int)dy.size(0),
-                              (int)w.size(1), (int)dy.size(1), 3, ep, cur_stream());
-  if (rc == -1) return false;
-  MX_OK(rc);
-  return true;
+  L.ep.gu = bf(gu);
+  L.ep.ldg = gu.stride(0);
+  return g8_launched("mx_gemm8_epi", mx_gemm8_epi(g8p(L.A), L.A.ld, g8p(L.B), L.B.ld, bfm(dgu), dgu.stride(0), L.M, L.N,
+                                                  L.K, mx::G8_EPI_SWIGLU_BWD, L.ep, cur_stream()));
 }
 
 // the gemm8 diagnostic build's cycle stamps (MXLLM_GEMM8_STAMPS): int64 [1024, 2, 80] on the host

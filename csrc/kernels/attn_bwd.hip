@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

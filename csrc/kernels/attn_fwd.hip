@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "bindings.h"
 #include "common.h"
 #include <stdlib.h>
 

@@ -10,6 +10,7 @@
 // Rows whose label == ignore_index, or lies outside [0, V), get loss 0 and a zero gradient row
 // and do not count in n_valid (ce_row_ignored: one predicate for the count and the row kernels).
 // n_valid is counted on device first (no host sync anywhere).
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

@@ -12,6 +12,7 @@
 // [blocks, Hkv, block, D] addressed through a per-slot block table (common.h
 // kv_row; the block size is a multiple of the 256-key decode split, so every
 // split reads one contiguous block).
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

@@ -6,6 +6,7 @@
 // <= 2048 workgroups x 256 threads (G11).
 #include <cstdlib>
 
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

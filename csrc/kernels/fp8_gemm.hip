@@ -21,6 +21,7 @@
 //  * the per-channel scale is applied once in the epilogue.
 #include <cstdlib>
 
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

@@ -47,6 +47,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {
@@ -61,7 +62,7 @@ __device__ __forceinline__ f32x4 g8_mfma(const u16x8& a, const u16x8& b, const f
 
 constexpr int G8_HT = 16384;        // one half-tile image: 128 rows (cols) x 64 k x bf16
 constexpr int G8_TILE = 4 * G8_HT;  // A0 | A1 | B0 | B1
-constexpr int G8_BK = 64;
+// G8_BK (64, the K-tile): gemm8_args.h
 
 // image row r' (k-contiguous) / image column (mn-contiguous) -> row / column of the 256 tile
 __device__ __forceinline__ int g8_map_b(int r, int h) { return (r >> 5) * 64 + h * 32 + (r & 31); }
@@ -86,22 +87,7 @@ __device__ __forceinline__ int g8_map_a(int r, int h) { return (r >> 6) * 128 + 
 //               place of dm (elementwise.hip swiglu_bwd / swiglu_bwd_m, fused away)
 // All round the GEMM result to bf16 first and then apply the exact expression of the kernel they
 // replace: bitwise equal to GEMM -> rope_split / swiglu_fwd / swiglu_bwd on the same kernel's output.
-constexpr int G8_EPI_NONE = 0, G8_EPI_ROPE = 1, G8_EPI_SWIGLU = 2, G8_EPI_SWIGLU_BWD = 3;
-
-struct G8Epi {
-  uint16_t* q;        // ROPE: [B, Hq, S, 128]
-  uint16_t* k;        //       [B, Hkv, S, 128]
-  uint16_t* v;        //       [B, Hkv, S, 128]
-  const float* cosb;  //       [>= S, 64] f32 (host table, mxllm/ops/reference.py rope_tables)
-  const float* sinb;
-  int S, Hq, Hkv;
-  uint16_t* m;        // SWIGLU: [T, F] with row stride ldm (SWIGLU_BWD: optional recomputed m)
-  int64_t ldm;
-  int F;
-  const uint16_t* gu; // SWIGLU_BWD: the forward's [T, 2F] with row stride ldg
-  int64_t ldg;
-  float* sq;          // plain bf16 beta-0 output: per-tile sum of squares of the stored values
-};
+// (G8EpiMode and the G8Epi argument block: gemm8_args.h)
 
 // weight row feeding virtual tile column v (0..255) of output tile pn (G8_EPI_SWIGLU: absolute row)
 template <int EPI>
@@ -1063,6 +1049,11 @@ gemm8p_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __res
 
 using namespace mx;
 
+// ---- host side ----------------------------------------------------------------------------------
+// Every entry point fills a G8Launch (gemm8_args.h), asks g8_takes -- the ONE check, before anything
+// is enqueued: -1 always means "nothing launched" -- and launches through g8_launch, the one map
+// from the runtime selectors to a template instantiation.
+
 // compute units of the current device (the persistent grid: one workgroup per CU)
 static int g8_cus() {
   static int n = 0;
@@ -1075,6 +1066,101 @@ static int g8_cus() {
   return n;
 }
 
+static G8Launch g8_desc(G8Entry entry, const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc,
+                        const void* C, int64_t ldc, int out_f32, int M, int N, int K) {
+  G8Launch L{};
+  L.entry = entry;
+  L.A = {A, lda, a_kc};
+  L.B = {B, ldb, b_kc};
+  L.C = {C, ldc, 1};
+  L.out_f32 = out_f32;
+  L.M = M, L.N = N, L.K = K;
+  L.alpha_f = 1.f;
+  return L;
+}
+
+// ---- the kernels this file builds, as tables: (A order, B order, output type, beta) -> instantiation.
+// Row i = 8 * !a_kc + 4 * !b_kc + 2 * !out_f32 + !beta.
+typedef void (*g8p_fn)(const uint16_t*, int64_t, const uint16_t*, int64_t, void*, int64_t, int, int, int, const float*,
+                       float);
+typedef void (*g8_fn)(const uint16_t*, int64_t, const uint16_t*, int64_t, void*, int64_t, int, int, int, const float*,
+                      float, int, int64_t, G8Epi);
+#define G8_ROWS(X)                                                                                            \
+  X(true, true, true, true) X(true, true, true, false) X(true, true, false, true) X(true, true, false, false) \
+  X(true, false, true, true) X(true, false, true, false) X(true, false, false, true)                          \
+  X(true, false, false, false) X(false, true, true, true) X(false, true, true, false)                         \
+  X(false, true, false, true) X(false, true, false, false) X(false, false, true, true)                        \
+  X(false, false, true, false) X(false, false, false, true) X(false, false, false, false)
+#define G8_ROW_P(AK, BK_, F, BT) gemm8p_kernel<AK, BK_, F, BT>,
+#define G8_ROW_K(AK, BK_, F, BT) {gemm8_kernel<AK, BK_, F, BT, 0, 4>, gemm8_kernel<AK, BK_, F, BT, 0, 8>},
+static const g8p_fn g8_persistent[16] = {G8_ROWS(G8_ROW_P)};  // 4-phase, persistent
+static const g8_fn g8_plain_k[16][2] = {G8_ROWS(G8_ROW_K)};   // [.][0]: 4-phase, [.][1]: 8-phase
+#undef G8_ROW_K
+#undef G8_ROW_P
+#undef G8_ROWS
+// the fused epilogues: one instantiation each -- its operand order, bf16, beta 0, 4-phase
+static g8_fn g8_epi_k(int epi) {
+  switch (epi) {
+    case G8_EPI_SWIGLU_BWD: return gemm8_kernel<true, false, false, false, 0, 4, G8_EPI_SWIGLU_BWD>;
+    case G8_EPI_ROPE: return gemm8_kernel<true, true, false, false, 0, 4, G8_EPI_ROPE>;
+    case G8_EPI_SWIGLU: return gemm8_kernel<true, true, false, false, 0, 4, G8_EPI_SWIGLU>;
+  }
+  return nullptr;
+}
+
+enum G8Sched { G8_S4 = 0, G8_S8 = 1, G8_S4_PERSIST };  // 4-phase, 8-phase, 4-phase persistent (grid = CUs)
+
+// THE map from a checked description to a kernel launch.  k0 / cpart: the half-K split (gridDim.y = 2).
+static void g8_launch(const G8Launch& L, G8Sched sched, dim3 grid, int k0, int64_t cpart, hipStream_t stream) {
+  const uint16_t* A = static_cast<const uint16_t*>(L.A.p);
+  const uint16_t* B = static_cast<const uint16_t*>(L.B.p);
+  void* C = const_cast<void*>(L.C.p);
+  const int row = (L.A.kc ? 0 : 8) + (L.B.kc ? 0 : 4) + (L.out_f32 ? 0 : 2) + (L.beta != 0.f ? 0 : 1);
+  if (sched == G8_S4_PERSIST) {
+    g8_persistent[row]<<<grid, 512, 0, stream>>>(A, L.A.ld, B, L.B.ld, C, L.C.ld, L.M, L.N, L.K, L.alpha_t, L.alpha_f);
+    return;
+  }
+  const g8_fn k = L.epi != G8_EPI_NONE ? g8_epi_k(L.epi) : g8_plain_k[row][sched];
+  k<<<grid, 512, 0, stream>>>(A, L.A.ld, B, L.B.ld, C, L.C.ld, L.M, L.N, L.K, L.alpha_t, L.alpha_f, k0, cpart, L.ep);
+}
+
+// the plain kernel on the schedule `L.ph` asks for; MXLLM_GEMM8_PH / MXLLM_GEMM8_PERSIST override it
+static int g8_plain(const G8Launch& L, hipStream_t stream) {
+  const int grid = (L.M >> 8) * (L.N >> 8);
+  const char* phs = getenv("MXLLM_GEMM8_PH");  // read per call: overrides `ph` (same-process A/B)
+  const bool ph4 = phs && *phs ? atoi(phs) == 4 : (L.ph == 4 || L.ph == 5);  // 5 = 4-phase, persistent
+#ifdef MXLLM_GEMM8_DIAG
+  if (L.A.kc && !L.B.kc && !L.out_f32 && L.beta == 0.f) {  // diagnostic variants: NN bf16 beta 0 only
+    const uint16_t* A = static_cast<const uint16_t*>(L.A.p);
+    const uint16_t* B = static_cast<const uint16_t*>(L.B.p);
+    void* C = const_cast<void*>(L.C.p);
+#define G8_DIAG(V, PH)                                                                                            \
+  (gemm8_kernel<true, false, false, false, V, PH><<<grid, 512, 0, stream>>>(A, L.A.ld, B, L.B.ld, C, L.C.ld, L.M, \
+                                                                            L.N, L.K, L.alpha_t, L.alpha_f),     \
+   (int)hipGetLastError())
+    const char* st = getenv("MXLLM_GEMM8_STAMPS");  // stamped build
+    if (st && grid <= 1024 && *st) return atoi(st) == 4 ? G8_DIAG(4, 4) : G8_DIAG(4, 8);
+    const char* ab = getenv("MXLLM_GEMM8_ABLATE");  // timing-only variants (results wrong)
+    const int v = ab ? atoi(ab) : 0;
+    if (v >= 1 && v <= 3) return v == 1 ? G8_DIAG(1, 8) : v == 2 ? G8_DIAG(2, 8) : G8_DIAG(3, 8);
+#undef G8_DIAG
+  }
+#endif
+  const char* pe = getenv("MXLLM_GEMM8_PERSIST");  // 1 = persistent 4-phase kernel (read per call: A/B)
+  const int persist = pe && *pe ? atoi(pe) : (L.ph == 5);
+  if (persist && ph4 && grid > g8_cus())
+    g8_launch(L, G8_S4_PERSIST, g8_cus(), 0, 0, stream);
+  else
+    g8_launch(L, ph4 ? G8_S4 : G8_S8, grid, 0, 0, stream);
+  return (int)hipGetLastError();
+}
+
+// the plain 4-phase kernel that also writes the per-tile sums of squares (L.ep.sq)
+static int g8_sq(const G8Launch& L, hipStream_t stream) {
+  g8_launch(L, G8_S4, (L.M >> 8) * (L.N >> 8), 0, 0, stream);
+  return (int)hipGetLastError();
+}
+
 // C[M, N] = alpha * op(A) op(B) + beta * C.  a_kc: A stored [M][K] (else [K][M]); b_kc: B stored [N][K]
 // (else [K][N]); row strides in elements.  Takes M, N multiples of 256; K a multiple of 64 when an
 // operand is k-contiguous (any K otherwise: rows past K read as zeros); 16-B aligned rows; beta 0 or 1;
@@ -1082,133 +1168,28 @@ static int g8_cus() {
 extern "C" int mx_gemm8(const uint16_t* A, int64_t lda, int a_kc, const uint16_t* B, int64_t ldb, int b_kc, void* C,
                         int64_t ldc, int out_f32, int M, int N, int K, float beta, const float* alpha_t, float alpha_f,
                         int ph, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || (M & 255) || (N & 255)) return -1;
-  if ((a_kc || b_kc) && (K % G8_BK)) return -1;
-  if (lda % 8 || ldb % 8 || ldc % 4 || ((uintptr_t)A | (uintptr_t)B) & 15 || ((uintptr_t)C & 15)) return -1;
-  if (a_kc ? lda < K : lda < M) return -1;
-  if (b_kc ? ldb < K : ldb < N) return -1;
-  if (ldc < N || (!out_f32 && ldc % 8)) return -1;  // bf16 epilogue: 16-B stores
-  if (beta != 0.f && beta != 1.f) return -1;
-  const int64_t kpad = (int64_t)((K + G8_BK - 1) / G8_BK) * G8_BK;
-  const int64_t aspan = a_kc ? 256 * lda : kpad * lda;
-  const int64_t bspan = b_kc ? 256 * ldb : kpad * ldb;
-  if (aspan * 2 >= ((int64_t)1 << 31) || bspan * 2 >= ((int64_t)1 << 31)) return -1;
-  const int grid = (M >> 8) * (N >> 8);
-  const bool acc = beta != 0.f;
-  const char* phs = getenv("MXLLM_GEMM8_PH");  // read per call: overrides `ph` (same-process A/B)
-  const bool ph4 = phs && *phs ? atoi(phs) == 4 : (ph == 4 || ph == 5);  // 5 = 4-phase, persistent
-#define G8_L(AK, BK_, F, BT)                                                                                        \
-  do {                                                                                                              \
-    if (ph4)                                                                                                        \
-      gemm8_kernel<AK, BK_, F, BT, 0, 4><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f); \
-    else                                                                                                            \
-      gemm8_kernel<AK, BK_, F, BT><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);      \
-  } while (0)
-#define G8_OUT(AK, BK_)                                        \
-  do {                                                         \
-    if (out_f32) {                                             \
-      if (acc) G8_L(AK, BK_, true, true); else G8_L(AK, BK_, true, false);   \
-    } else {                                                   \
-      if (acc) G8_L(AK, BK_, false, true); else G8_L(AK, BK_, false, false); \
-    }                                                          \
-  } while (0)
-#ifdef MXLLM_GEMM8_DIAG
-  if (const char* st = getenv("MXLLM_GEMM8_STAMPS")) {  // diagnostic stamped build, NN bf16 beta 0
-    if (a_kc && !b_kc && !out_f32 && !acc && grid <= 1024 && *st) {
-      if (atoi(st) == 4)
-        gemm8_kernel<true, false, false, false, 4, 4><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);
-      else
-        gemm8_kernel<true, false, false, false, 4, 8><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);
-      return (int)hipGetLastError();
-    }
-  }
-  if (const char* ab = getenv("MXLLM_GEMM8_ABLATE")) {  // timing-only variants, NN bf16 beta 0 (results wrong)
-    const int v = atoi(ab);
-    if (a_kc && !b_kc && !out_f32 && !acc && v >= 1 && v <= 3) {
-      if (v == 1)
-        gemm8_kernel<true, false, false, false, 1><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);
-      else if (v == 2)
-        gemm8_kernel<true, false, false, false, 2><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);
-      else
-        gemm8_kernel<true, false, false, false, 3><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f);
-      return (int)hipGetLastError();
-    }
-  }
-#endif
-  const char* pe = getenv("MXLLM_GEMM8_PERSIST");  // 1 = persistent 4-phase kernel (read per call: A/B)
-  const int persist = pe && *pe ? atoi(pe) : (ph == 5);
-  if (persist && ph4 && grid > g8_cus()) {
-    const int pg = g8_cus();
-#define G8_P(AK, BK_, F, BT) \
-  gemm8p_kernel<AK, BK_, F, BT><<<pg, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, alpha_f)
-#define G8_PO(AK, BK_)                                                       \
-  do {                                                                       \
-    if (out_f32) { if (acc) G8_P(AK, BK_, true, true); else G8_P(AK, BK_, true, false); }     \
-    else { if (acc) G8_P(AK, BK_, false, true); else G8_P(AK, BK_, false, false); }           \
-  } while (0)
-    if (a_kc && b_kc) G8_PO(true, true);
-    else if (a_kc) G8_PO(true, false);
-    else if (b_kc) G8_PO(false, true);
-    else G8_PO(false, false);
-#undef G8_PO
-#undef G8_P
-    return (int)hipGetLastError();
-  }
-  if (a_kc && b_kc)
-    G8_OUT(true, true);
-  else if (a_kc)
-    G8_OUT(true, false);
-  else if (b_kc)
-    G8_OUT(false, true);
-  else
-    G8_OUT(false, false);
-#undef G8_OUT
-#undef G8_L
-  return (int)hipGetLastError();
+  G8Launch L = g8_desc(G8_PLAIN, A, lda, a_kc, B, ldb, b_kc, C, ldc, out_f32, M, N, K);
+  L.beta = beta, L.alpha_t = alpha_t, L.alpha_f = alpha_f, L.ph = ph;
+  if (!g8_takes(L)) return -1;
+  return g8_plain(L, stream);
 }
 
-// Forward projection with a fused epilogue (G8Epi above), A = x [M][K] and B = W [N][K] both
-// k-contiguous, 4-phase schedule.  mode 1 (ROPE): N = (Hq + 2 Hkv) * 128, M = B * S, S % 256 == 0,
-// writes q / k / v head-major (C unused).  mode 2 (SWIGLU): N = 2F, F % 128 == 0, writes gu into C
-// [M][ldc >= 2F] and m into ep.m [M][ldm >= F].  mode 3 (SWIGLU_BWD, NN form: A = dy [M][K], B =
-// W_down [K][N]): dm -> dgu into C [M][ldc >= 2N] from ep.gu, and m into ep.m when set.  Returns -1
-// (nothing launched) for other shapes.
+// Projection with a fused epilogue (top of this file), 4-phase schedule, bf16 output.
+//  G8_EPI_ROPE (TN: A = x [M][K], B = W [N][K]): N = (Hq + 2 Hkv) * 128, M = B * S, S % 256 == 0;
+//    writes q / k / v head-major (C unused).
+//  G8_EPI_SWIGLU (TN): N = 2F, F % 128 == 0; writes gu into C [M][ldc >= 2F] and m into ep.m
+//    [M][ldm >= F].
+//  G8_EPI_SWIGLU_BWD (NN: A = dy [M][K], B = W_down [K][N]): dm -> dgu into C [M][ldc >= 2N] from
+//    ep.gu, and m into ep.m when set.
+// Returns -1 (nothing launched) for other modes and shapes.
 extern "C" int mx_gemm8_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc,
-                            int M, int N, int K, int mode, G8Epi ep, hipStream_t stream) {
-  if (mode == G8_EPI_SWIGLU_BWD) {
-    // NN: A = dy [M][K] k-contiguous, B = W_down [K][N] n-contiguous; C = dgu [M][ldc >= 2N]
-    if (M <= 0 || N <= 0 || K <= 0 || (M & 255) || (N & 255) || K % G8_BK) return -1;
-    if (lda % 8 || ldb % 8 || lda < K || ldb < N || ldc < 2 * (int64_t)N || ldc % 8 || !C || !ep.gu ||
-        ep.ldg < 2 * (int64_t)N || ep.ldg % 8 || (ep.m && (ep.ldm < N || ep.ldm % 8)) ||
-        (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)ep.gu | (uintptr_t)ep.m) & 15))
-      return -1;
-    if (256 * lda * 2 >= ((int64_t)1 << 31) || (int64_t)K * ldb * 2 >= ((int64_t)1 << 31)) return -1;
-    ep.F = N;
-    gemm8_kernel<true, false, false, false, 0, 4, G8_EPI_SWIGLU_BWD><<<(M >> 8) * (N >> 8), 512, 0, stream>>>(
-        A, lda, B, ldb, C, ldc, M, N, K, nullptr, 1.f, 0, 0, ep);
-    return (int)hipGetLastError();
-  }
-  if (M <= 0 || N <= 0 || K <= 0 || (M & 255) || (N & 255) || K % G8_BK) return -1;
-  if (lda % 8 || ldb % 8 || lda < K || ldb < K || ((uintptr_t)A | (uintptr_t)B) & 15) return -1;
-  const int64_t aspan = 256 * lda, bspan = (int64_t)N * ldb;
-  if (aspan * 2 >= ((int64_t)1 << 31) || bspan * 2 >= ((int64_t)1 << 31)) return -1;
-  const int grid = (M >> 8) * (N >> 8);
-  if (mode == G8_EPI_ROPE) {
-    if (N != (ep.Hq + 2 * ep.Hkv) * 128 || ep.S <= 0 || ep.S % 256 || M % ep.S || !ep.q || !ep.k || !ep.v ||
-        !ep.cosb || !ep.sinb || (((uintptr_t)ep.q | (uintptr_t)ep.k | (uintptr_t)ep.v) & 15))
-      return -1;
-    gemm8_kernel<true, true, false, false, 0, 4, G8_EPI_ROPE><<<grid, 512, 0, stream>>>(
-        A, lda, B, ldb, nullptr, 0, M, N, K, nullptr, 1.f, 0, 0, ep);
-  } else if (mode == G8_EPI_SWIGLU) {
-    if ((N / 2) % 128 || !C || !ep.m || ldc < N || ldc % 8 || ep.ldm < N / 2 || ep.ldm % 8 ||
-        (((uintptr_t)C | (uintptr_t)ep.m) & 15))
-      return -1;
-    ep.F = N / 2;
-    gemm8_kernel<true, true, false, false, 0, 4, G8_EPI_SWIGLU><<<grid, 512, 0, stream>>>(
-        A, lda, B, ldb, C, ldc, M, N, K, nullptr, 1.f, 0, 0, ep);
-  } else {
-    return -1;
-  }
+                            int M, int N, int K, G8EpiMode mode, G8Epi ep, hipStream_t stream) {
+  G8Launch L = g8_desc(G8_EPI, A, lda, 1, B, ldb, mode != G8_EPI_SWIGLU_BWD, C, ldc, 0, M, N, K);
+  L.epi = mode, L.ep = ep;
+  if (!g8_takes(L)) return -1;
+  if (mode == G8_EPI_ROPE) L.C = {nullptr, 0, 1};
+  else L.ep.F = mode == G8_EPI_SWIGLU ? N / 2 : N;
+  g8_launch(L, G8_S4, (M >> 8) * (N >> 8), 0, 0, stream);
   return (int)hipGetLastError();
 }
 
@@ -1219,28 +1200,10 @@ extern "C" int mx_gemm8_epi(const uint16_t* A, int64_t lda, const uint16_t* B, i
 extern "C" int mx_gemm8_sq(const uint16_t* A, int64_t lda, int a_kc, const uint16_t* B, int64_t ldb, int b_kc,
                            uint16_t* C, int64_t ldc, int M, int N, int K, const float* alpha_t, float alpha_f,
                            float* sq, hipStream_t stream) {
-  if (!sq || M <= 0 || N <= 0 || K <= 0 || (M & 255) || (N & 255)) return -1;
-  if ((a_kc || b_kc) && (K % G8_BK)) return -1;
-  if (lda % 8 || ldb % 8 || ldc % 8 || ((uintptr_t)A | (uintptr_t)B) & 15 || ((uintptr_t)C & 15)) return -1;
-  if (a_kc ? lda < K : lda < M) return -1;
-  if (b_kc ? ldb < K : ldb < N) return -1;
-  if (ldc < N) return -1;
-  const int64_t kpad = (int64_t)((K + G8_BK - 1) / G8_BK) * G8_BK;
-  const int64_t aspan = a_kc ? 256 * lda : kpad * lda;
-  const int64_t bspan = b_kc ? 256 * ldb : kpad * ldb;
-  if (aspan * 2 >= ((int64_t)1 << 31) || bspan * 2 >= ((int64_t)1 << 31)) return -1;
-  const int grid = (M >> 8) * (N >> 8);
-  G8Epi ep{};
-  ep.sq = sq;
-#define G8_SQ(AK, BK_)                                                                                           \
-  gemm8_kernel<AK, BK_, false, false, 0, 4><<<grid, 512, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, alpha_t, \
-                                                                     alpha_f, 0, 0, ep)
-  if (a_kc && b_kc) G8_SQ(true, true);
-  else if (a_kc) G8_SQ(true, false);
-  else if (b_kc) G8_SQ(false, true);
-  else G8_SQ(false, false);
-#undef G8_SQ
-  return (int)hipGetLastError();
+  G8Launch L = g8_desc(G8_SQ, A, lda, a_kc, B, ldb, b_kc, C, ldc, 0, M, N, K);
+  L.alpha_t = alpha_t, L.alpha_f = alpha_f, L.ep.sq = sq;
+  if (!g8_takes(L)) return -1;
+  return g8_sq(L, stream);
 }
 
 // C[m, c0 + n] = bf16(P0[m, n] + P1[m, n]) for the two K-part images of mx_gemm8_tail
@@ -1291,68 +1254,58 @@ __global__ void __launch_bounds__(256) g8_sum2_sq_kernel(const float* __restrict
   if (threadIdx.x == 0) sq[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The split part of a tail launch (L.rows / L.at): the output region past `at` as ONE launch of twice
+// as many workgroups, each over half of K (gridDim.y = 2; part 0 = floor(K-tiles / 2) tiles), into the
+// two fp32 images [M2][N2] in L.ws, `part` elements apart.  The caller's sum pass adds them.
+struct G8Split {
+  int M2, N2;
+  int64_t part;
+};
+static G8Split g8_launch_halfk(const G8Launch& L, bool ph4, hipStream_t stream) {
+  G8Launch S = g8_desc(G8_PLAIN, L.A.p, L.A.ld, L.A.kc, L.B.p, L.B.ld, L.B.kc, L.ws, 0, 1, L.M, L.N, L.K);
+  if (L.rows) {
+    const uint16_t* A = static_cast<const uint16_t*>(L.A.p);
+    S.A.p = L.A.kc ? A + (int64_t)L.at * L.A.ld : A + L.at;
+    S.M = L.M - L.at;
+  } else {
+    const uint16_t* B = static_cast<const uint16_t*>(L.B.p);
+    S.B.p = L.B.kc ? B + (int64_t)L.at * L.B.ld : B + L.at;
+    S.N = L.N - L.at;
+  }
+  S.C.ld = S.N;
+  const int k0 = (L.K / G8_BK / 2) * G8_BK;
+  const int64_t part = (int64_t)S.M * S.N;
+  g8_launch(S, ph4 ? G8_S4 : G8_S8, dim3((S.M >> 8) * (S.N >> 8), 2), k0, part, stream);
+  return {S.M, S.N, part};
+}
+
 // Tail-balanced bf16 GEMM, beta 0, alpha 1: C[M, N] = op(A) op(B) where the tile count leaves a last
 // wave of <= 128 tiles on the 256 CUs (e.g. the 70B qkv forward: 16 x 40 = 640 tiles).  The output is
 // split at `at` (columns, or rows when `rows`): [0, at) runs as one plain launch of whole waves; the
-// rest as ONE launch of twice as many workgroups, each over half of K (gridDim.y = 2), into two fp32
-// images in `ws` (2 * its element count); g8_sum2_kernel adds them in a fixed order into C
-// (deterministic).  The last wave then takes half a wave's time.  `at` and the rest multiples of 256.
+// rest as g8_launch_halfk into `ws` (2 * its element count); g8_sum2_kernel adds the two images in a
+// fixed order into C (deterministic).  The last wave then takes half a wave's time.  With `sq`: one
+// sum of squares per tile, the plain part's tiles first, then the split part's.
 extern "C" int mx_gemm8_tail(const uint16_t* A, int64_t lda, int a_kc, const uint16_t* B, int64_t ldb, int b_kc,
                              uint16_t* C, int64_t ldc, int M, int N, int K, int rows, int at, float* ws, int ph,
                              hipStream_t stream, float* sq) {
-  const int lim = rows ? M : N, rest = lim - at;
-  if (at <= 0 || rest <= 0 || (at & 255) || (rest & 255) || K < 2 * G8_BK) return -1;
-  if ((a_kc ? lda < K : lda < M) || (b_kc ? ldb < K : ldb < N) || ldb % 8 || lda % 8 || ldc % 8) return -1;
-  if (sq && (ph != 4 || (M & 255) || (N & 255))) return -1;  // partials: the 4-phase schedule, whole tiles
-  // every check of the split part BEFORE the plain part launches: a -1 after a launch would
-  // leave sq partials of a GEMM the caller then recomputes another way (a double-counted clip norm)
-  const uint16_t* A2 = rows ? (a_kc ? A + (int64_t)at * lda : A + at) : A;
-  const uint16_t* B2 = rows ? B : (b_kc ? B + (int64_t)at * ldb : B + at);
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)A2 | (uintptr_t)B2 | (uintptr_t)ws) & 15) return -1;
-  if ((a_kc || b_kc) && (K % G8_BK)) return -1;
-  {
-    const int64_t kpad = (int64_t)((K + G8_BK - 1) / G8_BK) * G8_BK;
-    const int64_t aspan = a_kc ? 256 * lda : kpad * lda, bspan = b_kc ? 256 * ldb : kpad * ldb;
-    if (aspan * 2 >= ((int64_t)1 << 31) || bspan * 2 >= ((int64_t)1 << 31) || ldc < N) return -1;
-  }
-  // plain part (sq: its tiles' partials first, then the split part's)
-  int rc;
-  if (sq)
-    rc = rows ? mx_gemm8_sq(A, lda, a_kc, B, ldb, b_kc, C, ldc, at, N, K, nullptr, 1.f, sq, stream)
-              : mx_gemm8_sq(A, lda, a_kc, B, ldb, b_kc, C, ldc, M, at, K, nullptr, 1.f, sq, stream);
-  else
-    rc = rows ? mx_gemm8(A, lda, a_kc, B, ldb, b_kc, C, ldc, 0, at, N, K, 0.f, nullptr, 1.f, ph, stream)
-              : mx_gemm8(A, lda, a_kc, B, ldb, b_kc, C, ldc, 0, M, at, K, 0.f, nullptr, 1.f, ph, stream);
+  G8Launch L = g8_desc(G8_TAIL, A, lda, a_kc, B, ldb, b_kc, C, ldc, 0, M, N, K);
+  L.rows = rows, L.at = at, L.ws = ws, L.ph = ph, L.ep.sq = sq;
+  if (!g8_takes(L)) return -1;
+  G8Launch P = L;  // plain part
+  (rows ? P.M : P.N) = at;
+  const int rc = sq ? g8_sq(P, stream) : g8_plain(P, stream);
   if (rc) return rc;
-  uint16_t* C2 = rows ? C + (int64_t)at * ldc : C + at;
-  const int M2 = rows ? rest : M, N2 = rows ? N : rest;
-  const int k0 = (K / G8_BK / 2) * G8_BK;  // part 0: floor(K-tiles / 2) tiles
-  const int64_t part = (int64_t)M2 * N2;
-  const dim3 grid((M2 >> 8) * (N2 >> 8), 2);
   const char* phs = getenv("MXLLM_GEMM8_PH");
-  const bool ph4 = phs && *phs ? atoi(phs) == 4 : ph == 4;
-#define G8_T(AK, BK_)                                                                                               \
-  do {                                                                                                              \
-    if (ph4)                                                                                                        \
-      gemm8_kernel<AK, BK_, true, false, 0, 4><<<grid, 512, 0, stream>>>(A2, lda, B2, ldb, ws, N2, M2, N2, K, nullptr, \
-                                                                         1.f, k0, part);                            \
-    else                                                                                                            \
-      gemm8_kernel<AK, BK_, true, false><<<grid, 512, 0, stream>>>(A2, lda, B2, ldb, ws, N2, M2, N2, K, nullptr, 1.f, \
-                                                                   k0, part);                                       \
-  } while (0)
-  if (a_kc && b_kc) G8_T(true, true);
-  else if (a_kc) G8_T(true, false);
-  else if (b_kc) G8_T(false, true);
-  else G8_T(false, false);
-#undef G8_T
+  const G8Split s = g8_launch_halfk(L, phs && *phs ? atoi(phs) == 4 : ph == 4, stream);
+  uint16_t* C2 = rows ? C + (int64_t)at * ldc : C + at;
   if (sq) {
-    const int64_t nplain = rows ? (int64_t)(at >> 8) * (N >> 8) : (int64_t)(M >> 8) * (at >> 8);
-    g8_sum2_sq_kernel<<<(M2 >> 8) * (N2 >> 8), 256, 0, stream>>>(ws, part, N2, C2, ldc, sq + nplain);
+    const int64_t nplain = (int64_t)(P.M >> 8) * (P.N >> 8);
+    g8_sum2_sq_kernel<<<(s.M2 >> 8) * (s.N2 >> 8), 256, 0, stream>>>(ws, s.part, s.N2, C2, ldc, sq + nplain);
     return (int)hipGetLastError();
   }
-  int64_t blocks = (part / 8 + 255) / 256;
+  int64_t blocks = (s.part / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  g8_sum2_kernel<<<(int)blocks, 256, 0, stream>>>(ws, part, N2, C2, ldc, part);
+  g8_sum2_kernel<<<(int)blocks, 256, 0, stream>>>(ws, s.part, s.N2, C2, ldc, s.part);
   return (int)hipGetLastError();
 }
 
@@ -1421,35 +1374,24 @@ __global__ void __launch_bounds__(256) g8_sum2_rope_kernel(const float* __restri
 
 // qkv projection (A = x [M][K], B = W [N][K], both k-contiguous; N = (Hq + 2 Hkv) * 128, M = B * S) with
 // the RoPE + head split fused, on the tail-balanced schedule of mx_gemm8_tail: columns [0, at) (whole
-// waves of tiles) through the G8_EPI_ROPE epilogue, columns [at, N) as twice as many half-K workgroups
-// into the two fp32 images in `ws` (2 * M * (N - at) floats), finished by g8_sum2_rope_kernel.  Removes
+// waves of tiles) through the G8_EPI_ROPE epilogue, columns [at, N) as g8_launch_halfk into the two
+// fp32 images in `ws` (2 * M * (N - at) floats), finished by g8_sum2_rope_kernel.  Removes
 // the qkv round trip through HBM and the rope_split pass of the LoRA-augmented qkv forward, whose GEMM
 // runs this tail-balanced launch anyway (70B: 16 x 40 tiles, `at` 8192 = the q heads).  Returns -1
 // (nothing launched) for shapes it does not take.
 extern "C" int mx_gemm8_rope_tail(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K,
                                   int at, float* ws, G8Epi ep, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K < 2 * G8_BK || (M & 255) || (N & 255) || K % G8_BK) return -1;
-  if (at <= 0 || at >= N || (at & 255)) return -1;
-  if (lda % 8 || ldb % 8 || lda < K || ldb < K || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)ws) & 15)) return -1;
-  const int64_t aspan = 256 * lda, bspan = (int64_t)N * ldb;
-  if (aspan * 2 >= ((int64_t)1 << 31) || bspan * 2 >= ((int64_t)1 << 31)) return -1;
-  if (N != (ep.Hq + 2 * ep.Hkv) * 128 || ep.S <= 0 || ep.S % 256 || M % ep.S || !ep.q || !ep.k || !ep.v ||
-      !ep.cosb || !ep.sinb || (((uintptr_t)ep.q | (uintptr_t)ep.k | (uintptr_t)ep.v) & 15) ||
-      (((uintptr_t)ep.cosb | (uintptr_t)ep.sinb) & 15))
-    return -1;
+  G8Launch L = g8_desc(G8_ROPE_TAIL, A, lda, 1, B, ldb, 1, nullptr, 0, 0, M, N, K);
+  L.epi = G8_EPI_ROPE, L.ep = ep, L.at = at, L.ws = ws;
+  if (!g8_takes(L)) return -1;
   // plain part: the epilogue writes q / k / v of the heads in [0, at) (tile pn covers heads 2 pn, 2 pn + 1)
-  gemm8_kernel<true, true, false, false, 0, 4, G8_EPI_ROPE><<<(M >> 8) * (at >> 8), 512, 0, stream>>>(
-      A, lda, B, ldb, nullptr, 0, M, at, K, nullptr, 1.f, 0, 0, ep);
-  // split part: columns [at, N), two half-K images
-  const int N2 = N - at;
-  const int k0 = (K / G8_BK / 2) * G8_BK;
-  const int64_t part = (int64_t)M * N2;
-  const dim3 grid((M >> 8) * (N2 >> 8), 2);
-  gemm8_kernel<true, true, true, false, 0, 4><<<grid, 512, 0, stream>>>(A, lda, B + (int64_t)at * ldb, ldb, ws, N2, M,
-                                                                        N2, K, nullptr, 1.f, k0, part);
-  int64_t blocks = ((int64_t)M * (N2 >> 7) * 8 + 255) / 256;
+  G8Launch P = L;
+  P.N = at;
+  g8_launch(P, G8_S4, (M >> 8) * (at >> 8), 0, 0, stream);
+  const G8Split s = g8_launch_halfk(L, true, stream);
+  int64_t blocks = ((int64_t)M * (s.N2 >> 7) * 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  g8_sum2_rope_kernel<<<(int)blocks, 256, 0, stream>>>(ws, part, N2, at, M, ep);
+  g8_sum2_rope_kernel<<<(int)blocks, 256, 0, stream>>>(ws, s.part, s.N2, at, M, ep);
   return (int)hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 //
 // token state: int32 [n_slots, V]; bits 0..30 = occurrences in the request's output,
 // bit 31 = "occurs in the prompt".
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

@@ -29,6 +29,7 @@
 // k-step identically for both operands).  Reference: the reference has no LoRA
 // path at all (fine-tuning is a planned-but-missing module,
 // reference src/distributed_inference.py:61-76); the math follows PEFT's LoRA.
+#include "bindings.h"
 #include "common.h"
 #include <stdlib.h>
 #include <string.h>

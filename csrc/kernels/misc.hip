@@ -3,6 +3,7 @@
 //    reference's per-prompt `torch.tensor([ord(c)...]).mean().item()`
 //    (reference src/utils.py:25-28).  One wave per segment, shuffle reduce.
 //  * scale/accumulate helpers used by the trainer (grad scaling, sq-norm).
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

@@ -41,6 +41,7 @@
 // consumes it can look valid) and stop; the host side checks the word after
 // synchronising on the communicator's last collective before the optimizer
 // reads a result (mxllm/parallel/comm.py ``verify``).
+#include "bindings.h"
 #include "common.h"
 
 namespace {

@@ -9,6 +9,7 @@
 // dγ: each backward workgroup walks ROWS rows with a fixed lane->column map, so
 // its γ-gradient partial stays in registers; partials [nblk, H] f32 are summed
 // by a second tiny kernel (two-stage, no atomics -> bitwise reproducible).
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

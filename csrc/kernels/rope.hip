@@ -9,6 +9,7 @@
 // cos/sin come from a host-precomputed f32 table [P, D/2] (no device trig).
 // "rotate-half" pairing: (x[i], x[i + D/2]).  Each lane owns 8 pairs = two
 // 16-B chunks.
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

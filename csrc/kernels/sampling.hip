@@ -23,6 +23,7 @@
 //    16-B loads.
 // The LDS mass histogram uses float atomics: a boundary whose cumulative mass
 // is within rounding of top_p * Z can move by one key between runs.
+#include "bindings.h"
 #include "common.h"
 
 namespace mx {

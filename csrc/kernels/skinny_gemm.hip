@@ -29,6 +29,7 @@
 //    rope_append launch of every layer.
 #include <cstdlib>
 
+#include "bindings.h"
 #include "common.h"
 #include "decode_fuse.h"
 

@@ -20,6 +20,7 @@
 // Every spin is bounded (s_memrealtime, 100 MHz): on timeout the kernel sets
 // the host-mapped error word, writes NaN results and exits, so a dead peer
 // cannot leave waves running on the GPU.
+#include "bindings.h"
 #include "common.h"
 
 namespace {

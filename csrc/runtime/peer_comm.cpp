@@ -27,14 +27,7 @@
 #include <cstring>
 #include <vector>
 
-extern "C" size_t mx_peer_staging_bytes(int world, int wgs, int slot_bytes);
-extern "C" size_t mx_peer_staging_bytes2(int world, int wgs, int slot_bytes, int64_t light_cap);
-extern "C" int mx_peer_collective_light(int mode, int dtype, int wire, char* const* lbases, const void* in, void* out,
-                                        int64_t n, int64_t m, int rank, int world, int wgs, int64_t light_cap,
-                                        uint32_t* epoch, int* err, long long timeout_ticks, hipStream_t stream);
-extern "C" int mx_peer_collective(int mode, int dtype, char* const* bases, const void* in, void* out, int64_t n,
-                                  int64_t m, int rank, int world, int wgs, int slot_bytes, uint32_t* epochs, int* err,
-                                  long long timeout_ticks, hipStream_t stream);
+#include "bindings.h"
 
 namespace {
 

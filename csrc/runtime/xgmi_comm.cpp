@@ -24,13 +24,7 @@
 #include <cstring>
 #include <vector>
 
-extern "C" int mx_xgmi_allreduce(uint32_t* const* flags, float* const* data, const float* in, float* out, int n,
-                                 int rank, int world, uint32_t epoch, int max_elems, int op, int* err,
-                                 long long timeout_ticks, hipStream_t stream);
-
-extern "C" int mx_xgmi_allreduce_bf16(uint32_t* const* flags, uint16_t* const* data, const uint16_t* in,
-                                      uint16_t* out, int n, int rank, int world, int max_elems, uint32_t* epochs,
-                                      int* err, long long timeout_ticks, hipStream_t stream);
+#include "bindings.h"
 
 namespace {
 

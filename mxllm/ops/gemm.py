@@ -94,11 +94,133 @@ def _policy() -> str:
     return os.environ.get("MXLLM_GEMM8", "table")
 
 
-def takes(form: str, M: int, N: int, K: int) -> bool:
-    """Shape constraints of the kernel (mirrors mx_gemm8)."""
-    if M % 256 or N % 256 or K <= 0:
+# (A k-contiguous, B k-contiguous) per form
+_KC = {"tn": (True, True), "nn": (True, False), "tt": (False, False), "nt": (False, True)}
+
+
+def g8_mat(t: torch.Tensor, kc: bool = True) -> tuple:
+    """A 2-D row-strided tensor as ``g8_takes`` reads an operand: (base address, row stride in
+    elements, k-contiguous).  Works on ``meta`` tensors (address 0)."""
+    return (t.data_ptr(), t.stride(0), bool(kc))
+
+
+def g8_shape_ok(a_kc: bool, b_kc: bool, M: int, N: int, K: int) -> bool:
+    """The shape rules of ``g8_takes``: whole 256 x 256 tiles; whole 64-wide K-tiles when an operand
+    is k-contiguous."""
+    return M > 0 and N > 0 and K > 0 and M % 256 == 0 and N % 256 == 0 and (K % 64 == 0 or not (a_kc or b_kc))
+
+
+def g8_takes(entry: str, A: tuple, B: tuple, C: tuple, M: int, N: int, K: int, *, out_f32: bool = False,
+             beta: float = 0.0, epi: str = "none", ep: dict | None = None, rows: bool = False, at: int = 0,
+             ws: int = 0, ph: int = 8, sq: int = 0) -> bool:
+    """Whether the gemm8 launcher ``entry`` ("plain", "sq", "epi", "tail", "rope_tail": mx_gemm8,
+    mx_gemm8_sq, ...) takes the launch -- the mirror of ``mx::g8_takes`` (csrc/kernels/gemm8_args.h,
+    rule for rule, in its order; tests/test_gemm8_args.py runs both over one grid).  ``A`` / ``B`` /
+    ``C``: ``g8_mat`` triples; ``epi``: "none", "rope", "swiglu", "swiglu_bwd"; ``ep``: the G8Epi
+    fields by name (addresses as ints, absent = 0); ``ws`` / ``sq``: addresses."""
+    e = ep or {}
+    (pa, lda, a_kc), (pb, ldb, b_kc), (pc, ldc, _) = A, B, C
+    tail = entry in ("tail", "rope_tail")
+    rope = entry in ("epi", "rope_tail") and epi == "rope"
+    swiglu = entry == "epi" and epi == "swiglu"
+    swiglu_bwd = entry == "epi" and epi == "swiglu_bwd"
+    if entry in ("epi", "rope_tail"):  # fused forward epilogues are TN, SWIGLU_BWD is NN
+        if not (rope or swiglu or swiglu_bwd) or not a_kc or b_kc == swiglu_bwd:
+            return False
+    elif epi != "none":
         return False
-    return K % 64 == 0 or form == "tt"
+    if not g8_shape_ok(a_kc, b_kc, M, N, K):
+        return False
+    if lda % 8 or ldb % 8 or pa % 16 or pb % 16:
+        return False
+    if lda < (K if a_kc else M) or ldb < (K if b_kc else N):
+        return False
+    # spans under 2^31 bytes: 256 rows of a k-contiguous operand, the K-tile-padded rows of an
+    # mn-contiguous one; the fused TN epilogues gather weight rows from the whole matrix (N rows)
+    kpad = (K + 63) // 64 * 64
+    if (256 if a_kc else kpad) * lda >= 2 ** 30:
+        return False
+    if ((N if rope or swiglu else 256) if b_kc else kpad) * ldb >= 2 ** 30:
+        return False
+    if beta not in (0.0, 1.0):
+        return False
+    if not rope and (pc % 16 or ldc % (4 if out_f32 else 8) or ldc < (2 * N if swiglu_bwd else N)):
+        return False
+    if entry == "sq" and not sq:
+        return False
+    if entry == "tail" and sq and ph != 4:
+        return False
+    if tail:
+        rest = (M if rows else N) - at
+        if K < 128 or at <= 0 or rest <= 0 or at % 256 or rest % 256 or ws % 16:
+            return False
+    if rope:
+        S = e.get("S", 0)
+        if N != (e.get("Hq", 0) + 2 * e.get("Hkv", 0)) * 128 or S <= 0 or S % 256 or M % S:
+            return False
+        if any(not e.get(f, 0) for f in ("q", "k", "v", "cosb", "sinb")) or any(e[f] % 16 for f in ("q", "k", "v")):
+            return False
+        if entry == "rope_tail" and (e["cosb"] % 16 or e["sinb"] % 16):
+            return False
+    if swiglu:
+        m, ldm = e.get("m", 0), e.get("ldm", 0)
+        if (N // 2) % 128 or not pc or not m or ldm < N // 2 or ldm % 8 or m % 16:
+            return False
+    if swiglu_bwd:
+        gu, ldg, m, ldm = e.get("gu", 0), e.get("ldg", 0), e.get("m", 0), e.get("ldm", 0)
+        if not pc or not gu or ldg < 2 * N or ldg % 8 or gu % 16:
+            return False
+        if m and (ldm < N or ldm % 8 or m % 16):
+            return False
+    return True
+
+
+_NEW = 16  # stands for a buffer the op allocates itself: non-null, 16-B aligned, contiguous
+
+
+def _row_major(*ts: torch.Tensor) -> bool:
+    """2-D with a unit inner stride: what the bindings require of every gemm8 operand."""
+    return all(t.dim() == 2 and t.stride(1) == 1 for t in ts)
+
+
+def g8_rope_takes(x2: torch.Tensor, w: torch.Tensor, S: int, Hq: int, Hkv: int, at: int = 0) -> bool:
+    """``g8_takes`` of the fused qkv projection x2 [B*S, K] @ w [(Hq + 2 Hkv) * 128, K]^T (gemm8_rope;
+    with ``at``: gemm8_rope_tail split at that column) into fresh q / k / v and 16-B aligned tables."""
+    ep = {"q": _NEW, "k": _NEW, "v": _NEW, "cosb": _NEW, "sinb": _NEW, "S": S, "Hq": Hq, "Hkv": Hkv}
+    return _row_major(x2, w) and g8_takes("rope_tail" if at else "epi", g8_mat(x2), g8_mat(w), (0, 0, True),
+                                          x2.shape[0], w.shape[0], x2.shape[1], epi="rope", ep=ep, at=at, ws=_NEW)
+
+
+def g8_swiglu_takes(x2: torch.Tensor, w: torch.Tensor) -> bool:
+    """``g8_takes`` of the fused gate-up projection x2 [T, K] @ w [2F, K]^T (gemm8_swiglu) into fresh
+    gu [T, 2F] and m [T, F]."""
+    N = w.shape[0]
+    return _row_major(x2, w) and g8_takes("epi", g8_mat(x2), g8_mat(w), (_NEW, N, True), x2.shape[0], N,
+                                          x2.shape[1], epi="swiglu", ep={"m": _NEW, "ldm": N // 2})
+
+
+def g8_swiglu_bwd_takes(T: int, wd: torch.Tensor) -> bool:
+    """``g8_takes`` of the down projection's dX GEMM with the SwiGLU backward fused (gemm8_swiglu_bwd):
+    a contiguous dy [T, H] and wd [H, F] into a fresh dgu [T, 2F], from a contiguous gu."""
+    if not _row_major(wd):
+        return False
+    H, F = wd.shape
+    return g8_takes("epi", (_NEW, H, True), g8_mat(wd, False), (_NEW, 2 * F, True), T, F, H, epi="swiglu_bwd",
+                    ep={"gu": _NEW, "ldg": 2 * F})
+
+
+def takes(form: str, M: int, N: int, K: int) -> bool:
+    """Shape constraints of the kernel: the shape rules of ``g8_takes`` (a dispatch decision sees
+    shapes only; strides, alignment and spans are the launcher's to refuse, and ``mm`` then falls
+    back)."""
+    return g8_shape_ok(*_KC[form], M, N, K)
+
+
+def tail_at(form: str, M: int, N: int, K: int, out_dtype: torch.dtype) -> int:
+    """The tail split this dispatch uses for the shape (the win table's ``tail`` entry; the sign
+    convention of ``tail_split``): > 0 a column, < 0 a row, 0 no tail-balanced launch."""
+    _table()
+    return _TAIL.get((form, M, N, K, "f32" if out_dtype == torch.float32 else "bf16"), 0)
 
 
 def schedule(form: str, M: int, N: int, K: int, out_dtype: torch.dtype) -> int:
@@ -119,10 +241,6 @@ DEFAULT_PH = int(os.environ.get("MXLLM_GEMM8_DEFAULT_PH", "4"))
 
 def want(form: str, M: int, N: int, K: int, out_dtype: torch.dtype) -> bool:
     return schedule(form, M, N, K, out_dtype) > 0
-
-
-# (A k-contiguous, B k-contiguous) per form
-_KC = {"tn": (True, True), "nn": (True, False), "tt": (False, False), "nt": (False, True)}
 
 
 def _dims(form, a, b):
@@ -149,7 +267,7 @@ def mm(form: str, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = N
           and odt in (torch.bfloat16, torch.float32) else 0)
     if ph:
         a_kc, b_kc = _KC[form]
-        t = _TAIL.get((form, M, N, K, "f32" if odt == torch.float32 else "bf16"), 0)
+        t = tail_at(form, M, N, K, odt)
         if (t and beta == 0.0 and alpha_t is None and odt == torch.bfloat16
                 and native().gemm8_tail(a, a_kc, b, b_kc, out, abs(t), t < 0, ph)):
             return out
@@ -180,7 +298,7 @@ def mm_sq(form: str, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, sq: to
     if schedule(form, M, N, K, torch.bfloat16) != 4:
         return False
     a_kc, b_kc = _KC[form]
-    t = _TAIL.get((form, M, N, K, "bf16"), 0)
+    t = tail_at(form, M, N, K, torch.bfloat16)
     if t and alpha_t is None:  # the tail-balanced launch, as ``mm`` takes it (its split part sums per tile)
         return bool(native().gemm8_tail(a, a_kc, b, b_kc, out, abs(t), t < 0, 4, sq))
     return bool(native().gemm8_sq(a, a_kc, b, b_kc, out, sq, alpha_t, 1.0))

@@ -250,8 +250,6 @@ def lora_qkv_attention_at(x: torch.Tensor, lin, B: int, S: int, Hq: int, Hkv: in
     with an augmented, non-transposed buffer) can run as ``lora_qkv_attention``: exactly when its
     unfused forward GEMM would run the tail-balanced gemm8 launch (the dispatch table's ``tail``
     entry for the augmented shape), whose RoPE variant then replaces GEMM + rope_split; 0 otherwise."""
-    from .fused import _g8_operands_ok
-
     if not (_LORA_QKV_ROPE and lin.lora_r > 0 and lin.augmented() and not lin.transposed and D == 128
             and S % 256 == 0 and use_native(x) and x.dtype == torch.bfloat16 and not gemm.deterministic()):
         return 0
@@ -260,14 +258,10 @@ def lora_qkv_attention_at(x: torch.Tensor, lin, B: int, S: int, Hq: int, Hkv: in
     if N != (Hq + 2 * Hkv) * D or x2.shape[0] != B * S or x2.shape[1] != K:
         return 0
     xa = _padded_rows(x2, pad)
-    if xa is None or not _g8_operands_ok(xa, lin.wbuf[:N, :]):
+    if xa is None or not gemm.schedule("tn", B * S, N, K + pad, torch.bfloat16):
         return 0
-    key = ("tn", B * S, N, K + pad, "bf16")
-    if not gemm.schedule("tn", B * S, N, K + pad, torch.bfloat16):
-        return 0
-    gemm._table()
-    at = gemm._TAIL.get(key, 0)
-    return at if at > 0 else 0
+    at = gemm.tail_at("tn", B * S, N, K + pad, torch.bfloat16)
+    return at if at > 0 and gemm.g8_rope_takes(xa, lin.wbuf[:N, :], S, Hq, Hkv, at) else 0
 
 
 def _lora_aug_input(x2, a, wbuf, amat, scaling, N, K, pad, nat):

@@ -177,6 +177,41 @@ def test_gemm8_tail_sq_partials(gpu, rows):
     assert torch.allclose(sq, want, rtol=1e-5, atol=0), (sq - want).abs().max().item()
 
 
+def test_refused_launch_enqueues_nothing(gpu):
+    """A launcher's refusal comes before anything is enqueued (one check up front, gemm8_args.h): the
+    smallest shapes where a refusal after the plain part had launched would leave partial results --
+    every output keeps its sentinel bit for bit."""
+    ops = _ops()
+
+    def sentinel(*shape, dtype=torch.bfloat16):
+        return torch.full(shape, -7.25, device=gpu, dtype=dtype)
+
+    def untouched(*ts):
+        torch.cuda.synchronize()
+        for t in ts:
+            bits = t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+            assert torch.equal(bits, torch.full_like(t, -7.25).view(bits.dtype))
+
+    # gemm8_tail with sq at M 256, N 512, K 64: K < 128 (the plain part alone would be taken)
+    out, sq = sentinel(256, 512), sentinel(2, dtype=torch.float32)
+    assert not ops.gemm8_tail(_mat(256, 64, gpu, seed=1), True, _mat(512, 64, gpu, seed=2), True, out, 256, False, 4,
+                              sq)
+    untouched(out, sq)
+    # gemm8_tail split at 128: not a whole tile
+    assert not ops.gemm8_tail(_mat(256, 128, gpu, seed=1), True, _mat(512, 128, gpu, seed=2), True, out, 128, False, 4)
+    untouched(out)
+    # gemm8_rope_tail at B 1, S 256, Hq 2, Hkv 1, K 128 split at 128
+    q, k, v = sentinel(1, 2, 256, 128), sentinel(1, 1, 256, 128), sentinel(1, 1, 256, 128)
+    cos, sin = torch.ones(256, 64, device=gpu), torch.zeros(256, 64, device=gpu)
+    assert not ops.gemm8_rope_tail(_mat(256, 128, gpu, seed=1), _mat(512, 128, gpu, seed=2), cos, sin, 1, 256, 2, 1, q,
+                                   k, v, 128)
+    untouched(q, k, v)
+    # gemm8_swiglu with F = 64: N = 128 is no whole tile
+    gu, m = sentinel(256, 128), sentinel(256, 64)
+    assert not ops.gemm8_swiglu(_mat(256, 64, gpu, seed=1), _mat(128, 64, gpu, seed=2), gu, m)
+    untouched(gu, m)
+
+
 def test_gemm_dispatch_uses_tail_entry(gpu, monkeypatch):
     """A win-table entry with ``tail`` routes the forward GEMM through the tail-balanced launch."""
     from mxllm.ops import gemm

@@ -411,13 +411,13 @@ def test_fused_epilogue_predicates_match_native_limits():
     """the fused-epilogue predicates check what mx_gemm8_epi declines (strides,
     alignment, the 2^31-byte operand spans), so a predicate that says yes is never met by a
     declined launch; a 405B-class gate-up weight stays on the unfused path."""
-    from mxllm.ops.fused import _g8_operands_ok
+    from mxllm.ops.gemm import g8_swiglu_takes
 
     x = torch.empty(4096, 8192, dtype=torch.bfloat16, device="meta")
-    assert _g8_operands_ok(x, torch.empty(57344, 8192, dtype=torch.bfloat16, device="meta"))  # 70B gate-up
-    assert not _g8_operands_ok(torch.empty(4096, 16384, dtype=torch.bfloat16, device="meta"),
+    assert g8_swiglu_takes(x, torch.empty(57344, 8192, dtype=torch.bfloat16, device="meta"))  # 70B gate-up
+    assert not g8_swiglu_takes(torch.empty(4096, 16384, dtype=torch.bfloat16, device="meta"),
                                torch.empty(106496, 16384, dtype=torch.bfloat16, device="meta"))
-    assert not _g8_operands_ok(torch.empty(4096, 8196, dtype=torch.bfloat16, device="meta")[:, :8192],
+    assert not g8_swiglu_takes(torch.empty(4096, 8196, dtype=torch.bfloat16, device="meta")[:, :8192],
                                torch.empty(57344, 8192, dtype=torch.bfloat16, device="meta"))  # lda % 8
 
 
