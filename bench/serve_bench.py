@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--kv-pool-tokens", type=int, default=None,
                     help="paged KV cache shared by all slots (default: every slot owns max_seq positions)")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: e4m3 KV cache with one f32 scale per (token, KV head) row")
     ap.add_argument("--tp-shard-proxy", type=int, default=0,
                     help="one GPU: run rank 0's TP-N shard without the collectives (per-GPU compute floor)")
     a = ap.parse_args()
@@ -91,7 +93,8 @@ def main():
         sum(b.numel() * b.element_size() for n, b in model.named_buffers() if n.endswith((".q", ".scale")))
     bmax = max(int(b) for b in a.batches.split(","))
     max_seq = max(a.prompt_len, a.ctx + a.decode_steps, a.e2e_prompt_len + a.new_tokens) + 8
-    eng = Engine(model, max_batch=max(bmax, 1), max_seq=max_seq, tp_group=tp_group, kv_pool_tokens=a.kv_pool_tokens)
+    eng = Engine(model, max_batch=max(bmax, 1), max_seq=max_seq, tp_group=tp_group, kv_pool_tokens=a.kv_pool_tokens,
+                 kv_dtype=a.kv_cache)
     g = torch.Generator().manual_seed(0)
 
     def prompt(n):
@@ -113,7 +116,7 @@ def main():
                                if world > 1 else
                                {"tp": a.tp_shard_proxy, "collectives": "omitted (one-GPU shard proxy)"}
                                if a.tp_shard_proxy > 1 else None),
-           "weights_gb": round(wbytes / 1e9, 1), "init_s": round(init_s, 1),
+           "kv_cache_dtype": eng.kv_dtype, "weights_gb": round(wbytes / 1e9, 1), "init_s": round(init_s, 1),
            "prefill": {"prompt_len": a.prompt_len, "ttft_ms": round(1e3 * pre_s, 2),
                        "tokens_per_s": round(a.prompt_len / pre_s, 1)},
            "decode": []}
@@ -135,7 +138,8 @@ def main():
             eng.decode(slots, tok)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t) / a.decode_steps
-        kv_bytes = bs * (a.ctx + a.decode_steps // 2) * cfg.n_layers * 2 * cfg.n_kv_heads * cfg.head_dim * 2
+        row_bytes = cfg.head_dim + 4 if eng.kv.fp8 else cfg.head_dim * 2  # fp8: codes + one f32 scale
+        kv_bytes = bs * (a.ctx + a.decode_steps // 2) * cfg.n_layers * 2 * cfg.n_kv_heads * row_bytes
         out["decode"].append({"batch": bs, "ctx": a.ctx, "ms_per_step": round(1e3 * dt, 3),
                               "tokens_per_s": round(bs / dt, 1),
                               "weight_stream_tb_s": round(wbytes / dt / 1e12, 2),

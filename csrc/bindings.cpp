@@ -912,6 +912,101 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at:
   return out;
 }
 
+// ---------------------------------------------------------------- kv8: fp8 (e4m3) KV cache, head_dim 128
+// Pools of one layer: codes uint8 [rows, Hkv, SEQ, 128] and scales f32 [rows, Hkv, SEQ] for K and
+// for V (contiguous or paged like the bf16 caches).  Every check runs before anything is written.
+static void check_kv8_pools(const at::Tensor& k_codes, const at::Tensor& k_scale, const at::Tensor& v_codes,
+                            const at::Tensor& v_scale, const at::Device& dev, int64_t Hkv, const char* op) {
+  for (const at::Tensor* c : {&k_codes, &v_codes})
+    MX_CHECK(c->device() == dev && c->scalar_type() == at::kByte && c->is_contiguous() && c->dim() == 4, op,
+             ": code pools must be contiguous uint8 [rows, Hkv, SEQ, 128] on the query's device");
+  MX_CHECK(k_codes.size(3) == 128, op, ": the fp8 KV cache supports head_dim 128 only, got ", k_codes.size(3));
+  MX_CHECK(k_codes.size(1) == Hkv, op, ": code pools hold ", k_codes.size(1), " KV heads, expected ", Hkv);
+  MX_CHECK(v_codes.sizes() == k_codes.sizes(), op, ": k_codes and v_codes differ in shape");
+  for (const at::Tensor* s : {&k_scale, &v_scale})
+    MX_CHECK(s->device() == dev && s->scalar_type() == at::kFloat && s->is_contiguous() && s->dim() == 3 &&
+                 s->size(0) == k_codes.size(0) && s->size(1) == Hkv && s->size(2) == k_codes.size(2),
+             op, ": scale pools must be contiguous float32 [rows, Hkv, SEQ] matching the code pools");
+}
+static const int32_t* check_rows_i32(const c10::optional<at::Tensor>& t, const at::Device& dev, int64_t B,
+                                     const char* op, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  MX_CHECK(t->device() == dev && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == B, op, ": ", name,
+           " must be a contiguous int32 [B] tensor on the query's device");
+  return t->data_ptr<int32_t>();
+}
+
+// x [R, 128] bf16 rows (row stride a multiple of 8) -> (codes uint8 [R, 128], scale f32 [R])
+std::tuple<at::Tensor, at::Tensor> kv8_quant_rows(const at::Tensor& x) {
+  MX_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.size(1) == 128 &&
+               (x.size(0) <= 1 || (x.stride(0) >= 128 && x.stride(0) % 8 == 0)) && x.stride(1) == 1,
+           "kv8_quant_rows: x must be bf16 [R, 128] rows on the GPU with a row stride that is a multiple of 8");
+  DevGuard g(x.device());
+  const int64_t R = x.size(0);
+  auto q = at::empty({R, 128}, x.options().dtype(at::kByte));
+  auto s = at::empty({R}, x.options().dtype(at::kFloat));
+  MX_OK(mx_kv8_quant_rows(bf(x), R <= 1 ? 128 : x.stride(0), q.data_ptr<uint8_t>(), s.data_ptr<float>(), R,
+                          cur_stream()));
+  return {q, s};
+}
+
+// rope_append into kv8 pools; returns the rotated q [B, Hq, 128] (rope_append's q)
+at::Tensor rope_append_kv8(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                           const c10::optional<at::Tensor>& slots, at::Tensor k_codes, at::Tensor k_scale,
+                           at::Tensor v_codes, at::Tensor v_scale, int64_t Hq, int64_t Hkv,
+                           const c10::optional<at::Tensor>& block_table) {
+  check_bf16(qkv, "qkv");
+  MX_CHECK(qkv.dim() == 2 && Hq > 0 && Hkv > 0 && qkv.size(1) == (Hq + 2 * Hkv) * 128,
+           "rope_append_kv8: qkv must be [B, (Hq + 2 Hkv) * 128] (head_dim 128 only)");
+  const int64_t B = qkv.size(0);
+  check_kv8_pools(k_codes, k_scale, v_codes, v_scale, qkv.device(), Hkv, "rope_append_kv8");
+  for (const at::Tensor* t : {&cos, &sin})
+    MX_CHECK(t->device() == qkv.device() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
+                 t->size(1) == 64,
+             "rope_append_kv8: cos / sin must be contiguous float32 [positions, 64] on qkv's device");
+  MX_CHECK(pos.defined(), "rope_append_kv8: pos");
+  const int32_t* pp = check_rows_i32(pos, qkv.device(), B, "rope_append_kv8", "pos");
+  const int32_t* sl = check_rows_i32(slots, qkv.device(), B, "rope_append_kv8", "slots");
+  DevGuard g(qkv.device());
+  const KvPages pg = kv_pages(block_table, k_codes);
+  auto q = at::empty({B, Hq, 128}, qkv.options());
+  MX_OK(mx_rope_append_kv8(bf(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), pp, sl, bfm(q),
+                           k_codes.data_ptr<uint8_t>(), k_scale.data_ptr<float>(), v_codes.data_ptr<uint8_t>(),
+                           v_scale.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv, (int)k_codes.size(2), pg.bt, pg.maxb,
+                           cur_stream()));
+  return q;
+}
+
+// decode_attn over kv8 pools: q [B, Hq, 128] -> out [B, Hq * 128]
+at::Tensor decode_attn_kv8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& k_scale,
+                           const at::Tensor& v_codes, const at::Tensor& v_scale, const at::Tensor& lens,
+                           const c10::optional<at::Tensor>& slots, int64_t max_len, double scale, int64_t len_off,
+                           const c10::optional<at::Tensor>& block_table) {
+  check_bf16(q, "q");
+  MX_CHECK(q.dim() == 3 && q.size(2) == 128, "decode_attn_kv8: q must be [B, Hq, 128] (head_dim 128 only)");
+  const int64_t B = q.size(0), Hq = q.size(1);
+  MX_CHECK(k_codes.dim() == 4, "decode_attn_kv8: code pools must be uint8 [rows, Hkv, SEQ, 128]");
+  const int64_t Hkv = k_codes.size(1), max_seq = k_codes.size(2);
+  check_kv8_pools(k_codes, k_scale, v_codes, v_scale, q.device(), Hkv, "decode_attn_kv8");
+  MX_CHECK(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, "decode_attn_kv8: ", Hq, " q-heads over ", Hkv,
+           " KV heads: the group size must be a whole number of at most 16");
+  MX_CHECK(lens.defined(), "decode_attn_kv8: lens");
+  const int32_t* lp = check_rows_i32(lens, q.device(), B, "decode_attn_kv8", "lens");
+  const int32_t* sl = check_rows_i32(slots, q.device(), B, "decode_attn_kv8", "slots");
+  DevGuard g(q.device());
+  const KvPages pg = kv_pages(block_table, k_codes);
+  const int64_t cap = pg.bt ? (int64_t)pg.maxb * max_seq : max_seq;  // positions a sequence can hold
+  const int64_t nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);
+  auto ml = at::empty({B, Hq, nsplit, 2}, q.options().dtype(at::kFloat));
+  auto po = at::empty({B, Hq, nsplit, 128}, q.options().dtype(at::kFloat));
+  auto out = at::empty({B, Hq * 128}, q.options());
+  MX_OK(mx_decode_attn_kv8(bf(q), k_codes.data_ptr<uint8_t>(), k_scale.data_ptr<float>(), v_codes.data_ptr<uint8_t>(),
+                           v_scale.data_ptr<float>(), lp, (int)len_off, sl, ml.data_ptr<float>(), po.data_ptr<float>(),
+                           bfm(out), (int)B, (int)Hq, (int)Hkv, (int)max_seq, (int)nsplit, (float)scale, pg.bt, pg.maxb,
+                           cur_stream()));
+  return out;
+}
+
 // The split-K partials without the combine: (part_ml [B, Hq, nsplit, 2], part_o [B, Hq, nsplit, D]),
 // merged by the o-projection's prologue (skinny_merge_linear).  D = 128.
 std::tuple<at::Tensor, at::Tensor> decode_attn_partials(const at::Tensor& q, const at::Tensor& k_cache,
@@ -1342,6 +1437,9 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("rope_append(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_cache, Tensor(b!) v_cache, int Hq, int Hkv, int D, Tensor? block_table=None) -> Tensor");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None, Tensor? counters=None) -> Tensor");
   m.def("decode_attn_partials(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> (Tensor, Tensor)");
+  m.def("kv8_quant_rows(Tensor x) -> (Tensor, Tensor)");
+  m.def("rope_append_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_codes, Tensor(b!) k_scale, Tensor(c!) v_codes, Tensor(d!) v_scale, int Hq, int Hkv, Tensor? block_table=None) -> Tensor");
+  m.def("decode_attn_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> Tensor");
   m.def("skinny_merge_linear(Tensor ml, Tensor po, Tensor w) -> Tensor");
   m.def("sample(Tensor logits, float temperature, int seed, int step) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temps, Tensor top_p, Tensor top_k, Tensor seeds, Tensor steps) -> Tensor");
@@ -1403,6 +1501,9 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("decode_attn_partials", &decode_attn_partials);
   m.impl("skinny_merge_linear", &skinny_merge_linear);
   m.impl("decode_attn", &decode_attn);
+  m.impl("kv8_quant_rows", &kv8_quant_rows);
+  m.impl("rope_append_kv8", &rope_append_kv8);
+  m.impl("decode_attn_kv8", &decode_attn_kv8);
   m.impl("sample", &sample);
   m.impl("sample_rows", &sample_rows);
   m.impl("sample_temp_rows", &sample_temp_rows);

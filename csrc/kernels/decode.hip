@@ -5,6 +5,8 @@
 //                   each workgroup streams 256 keys of one (seq, kv-head) once
 //                   and serves all q-heads of that group (GQA reuse);
 //   * decode_combine : merges the per-split (m, l, o) partials;
+//   * kv8_quant_rows / rope_append_kv8 / decode_attn_kv8 : the same append and attention
+//                   over an fp8 (e4m3) cache with one power-of-two scale per row;
 //   * sample : greedy argmax or exact temperature sampling via Gumbel-max with
 //              a counter-based hash RNG (one pass, no softmax materialised).
 // KV cache layout per layer: [slots, Hkv, max_seq, D] bf16 (contiguous per slot
@@ -504,6 +506,307 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
   out[bh * D + d] = f2bf(L > 0.f ? acc / L : 0.f);
 }
 
+// ---------------------------------------------------------------------------
+// kv8: fp8 (OCP e4m3) KV cache, head_dim 128 (format: mxllm/serve/quant.py kv8_quantize).
+// A row = the 128 values of one (token, kv-head): 128 e4m3 codes and one f32 scale 2^e, the
+// smallest power of two with amax / 2^e <= 448.  Code pools [rows, Hkv, SEQ, 128] u8 and scale
+// pools [rows, Hkv, SEQ] f32 are both addressed by kv_row (x 128 and x 1).  x * 2^-e is exact, the
+// hardware pack conversion rounds to nearest even and keeps zero and subnormals; code * 2^e is a
+// bf16 value, so decoding is exact and the dequantised cache is a bf16 cache.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kKv8MinExp = -100;
+
+// e of a row's scale 2^e from the largest bf16 magnitude of the row (its bits without the sign):
+// amax = m 2^E, 1 <= m < 2: E - 8 if m <= 1.75, else E - 7
+__device__ __forceinline__ int kv8_exp(uint32_t amax_bits) {
+  if (amax_bits == 0) return 0;
+  return max((int)(amax_bits >> 7) - 135 + ((amax_bits & 0x7Fu) > 0x60u ? 1 : 0), kKv8MinExp);
+}
+__device__ __forceinline__ float kv8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+__device__ __forceinline__ uint32_t kv8_amax8(const u16x8& v) {
+  uint32_t a = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a = max(a, (uint32_t)v[j] & 0x7FFFu);
+  return a;
+}
+// 8 bf16 values times inv (a power of two) -> 8 e4m3 codes
+__device__ __forceinline__ uint2 kv8_pack8(const u16x8& v, float inv) {
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]) * inv, bf2f(v[1]) * inv, lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]) * inv, bf2f(v[3]) * inv, lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]) * inv, bf2f(v[5]) * inv, hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]) * inv, bf2f(v[7]) * inv, hi, true);
+  return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+// 8 e4m3 codes times sc (a power of two) -> 8 bf16: the hardware conversion is exact for every
+// code (subnormals included) and the product has 4 significant bits, so the bf16 is the upper
+// half of the f32
+__device__ __forceinline__ uint32_t kv8_hi2(float a, float b) {
+  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+}
+__device__ __forceinline__ u16x8 kv8_dec8(uint32_t lo, uint32_t hi, float sc) {
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  return __builtin_bit_cast(u16x8, u32x4{kv8_hi2(a[0] * sc, a[1] * sc), kv8_hi2(b[0] * sc, b[1] * sc),
+                                         kv8_hi2(c[0] * sc, c[1] * sc), kv8_hi2(d[0] * sc, d[1] * sc)});
+}
+__device__ __forceinline__ u16x8 kv8_dec8(uint32_t lo, uint32_t hi) {
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  return __builtin_bit_cast(u16x8, u32x4{kv8_hi2(a[0], a[1]), kv8_hi2(b[0], b[1]), kv8_hi2(c[0], c[1]),
+                                         kv8_hi2(d[0], d[1])});
+}
+
+// X [R, 128] bf16 rows (stride ldx) -> codes [R, 128], scales [R]: 16 lanes per row (8 values
+// each), four rows per wave, the row's amax by shuffles inside the lane group
+__global__ void __launch_bounds__(256) kv8_quant_rows_kernel(const uint16_t* __restrict__ X, int64_t ldx,
+                                                             uint8_t* __restrict__ Q, float* __restrict__ S,
+                                                             int64_t R) {
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int cc = threadIdx.x & 15;
+  if (row >= R) return;  // whole 16-lane groups leave
+  const u16x8 v = *reinterpret_cast<const u16x8*>(X + row * ldx + cc * 8);
+  uint32_t am = kv8_amax8(v);
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+  const int e = kv8_exp(am);
+  *reinterpret_cast<uint2*>(Q + row * 128 + cc * 8) = kv8_pack8(v, kv8_pow2(-e));
+  if (cc == 0) S[row] = kv8_pow2(e);
+}
+
+// rope_append_kernel<128> into a kv8 cache: the same items (8 lanes per (row, head), each with
+// the value chunks c and c + 64 of a rotation pair) and the same arithmetic; the K row is rounded
+// to bf16 as rope_append stores it and then quantised like a V row, the row's amax by shuffles
+// over the 8 lanes.  q is rope_append's q.
+__global__ void __launch_bounds__(256) rope_append_kv8_kernel(
+    const uint16_t* __restrict__ qkv, const float* __restrict__ cosb, const float* __restrict__ sinb,
+    const int32_t* __restrict__ pos, const int32_t* __restrict__ slots, uint16_t* __restrict__ q,
+    uint8_t* __restrict__ kq, float* __restrict__ ks, uint8_t* __restrict__ vq, float* __restrict__ vs, int B, int Hq,
+    int Hkv, int max_seq, const int32_t* __restrict__ bt, int maxb) {
+  constexpr int D = 128, HALF = D / 2, CPH = HALF / 8;
+  const int NH = Hq + 2 * Hkv;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * NH * CPH) return;  // whole 8-lane groups leave
+  const int cc = (int)(i % CPH);
+  const int head = (int)((i / CPH) % NH);
+  const int b = (int)(i / ((int64_t)CPH * NH));
+  const int c = cc * 8;
+  const int p = pos[b];
+  const int slot = slots ? slots[b] : b;
+  const uint16_t* src = qkv + (int64_t)b * NH * D + (int64_t)head * D;
+  const u16x8 x1 = *reinterpret_cast<const u16x8*>(src + c);
+  const u16x8 x2 = *reinterpret_cast<const u16x8*>(src + HALF + c);
+  u16x8 y1 = x1, y2 = x2;
+  if (head < Hq + Hkv) {
+    const float* cp = cosb + (int64_t)p * HALF + c;
+    const float* sp = sinb + (int64_t)p * HALF + c;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float a = bf2f(x1[j]), bb = bf2f(x2[j]);
+      y1[j] = f2bf(a * cp[j] - bb * sp[j]);
+      y2[j] = f2bf(bb * cp[j] + a * sp[j]);
+    }
+  }
+  if (head < Hq) {
+    uint16_t* dst = q + ((int64_t)b * Hq + head) * D;
+    *reinterpret_cast<u16x8*>(dst + c) = y1;
+    *reinterpret_cast<u16x8*>(dst + HALF + c) = y2;
+    return;
+  }
+  uint32_t am = max(kv8_amax8(y1), kv8_amax8(y2));
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+  const int e = kv8_exp(am);
+  const float inv = kv8_pow2(-e);
+  const bool isv = head >= Hq + Hkv;
+  const int64_t r = kv_row(bt, maxb, max_seq, slot, Hkv, head - Hq - (isv ? Hkv : 0), p);
+  uint8_t* dst = (isv ? vq : kq) + r * D;
+  *reinterpret_cast<uint2*>(dst + c) = kv8_pack8(y1, inv);
+  *reinterpret_cast<uint2*>(dst + HALF + c) = kv8_pack8(y2, inv);
+  if (cc == 0) (isv ? vs : ks)[r] = kv8_pow2(e);
+}
+
+// decode_split_body over a kv8 cache: the same partition (256 keys per workgroup, 64 per wave),
+// MFMAs, softmax, V image and wave merge.  What differs:
+//   * K codes go from HBM into registers, 16 per lane and load: lane (c, g) holds
+//     K[key][64 sp + 16 g .. +15]; k-step s = 2 sp + h takes its bytes 8 h .. 8 h + 7, decoded to
+//     bf16 in registers, and the Q^T fragment of that k-step holds the same 8 dimensions;
+//   * the score of a key is multiplied by the key's K scale (a power of two: exact) before the
+//     softmax scale;
+//   * V codes are loaded to registers (row 8 seg + lane / 8, 16 codes per lane), decoded,
+//     multiplied by the row's V scale and written to the swizzled bf16 image that the
+//     transposed reads expect.
+// Keys at or past k_hi are never loaded, codes or scales: the index is clamped to k_hi - 1.
+__device__ __forceinline__ void decode_split_body_kv8(
+    const uint16_t* __restrict__ q, const uint8_t* __restrict__ kq, const float* __restrict__ ksc,
+    const uint8_t* __restrict__ vq, const float* __restrict__ vsc, float* __restrict__ part_o, float* __restrict__ pml,
+    char* smem, float (*mls)[2][16], int b, int hk, int rep, int Hq, int split, int nsplit, int k_lo, int k_hi,
+    int slot, int max_seq, float sl, const int32_t* __restrict__ bt, int maxb, int Hkv) {
+  constexpr int D = 128, ROWB = 256, WKEYS = 64, WTILE = WKEYS * ROWB;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 15, g = lane >> 4;
+  const int64_t rb = kv_row(bt, maxb, max_seq, slot, Hkv, hk, k_lo) - k_lo;  // rb + key: every key of this split
+  const uint8_t* kbase = kq + rb * D;
+  const uint8_t* vbase = vq + rb * D;
+  const float* ksb = ksc + rb;
+  const float* vsb = vsc + rb;
+  const int wk0 = k_lo + WKEYS * w;
+  char* vs = smem + w * WTILE;
+
+  u32x4 vreg[8];
+  float vscl[8];
+#pragma unroll
+  for (int seg = 0; seg < 8; ++seg) {
+    const int key = min(wk0 + seg * 8 + (lane >> 3), k_hi - 1);
+    vreg[seg] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * D + 16 * (lane & 7));
+    vscl[seg] = vsb[key];
+  }
+  u32x4 kreg[4][2];
+  float kscl[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int key = min(wk0 + 16 * j + c, k_hi - 1);
+#pragma unroll
+    for (int sp = 0; sp < 2; ++sp)
+      kreg[j][sp] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)key * D + 64 * sp + 16 * g);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) kscl[j][i] = ksb[min(wk0 + 16 * j + 4 * g + i, k_hi - 1)];
+  }
+  // Q^T fragments (B operand): lane (c, g), k-step s = 2 sp + h holds Q[head c][64 sp + 16 g + 8 h .. +7]
+  u16x8 qf[4];
+  const uint16_t* qrow = q + ((int64_t)b * Hq + hk * rep + min(c, rep - 1)) * D;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    qf[s] = *reinterpret_cast<const u16x8*>(qrow + 64 * (s >> 1) + 16 * g + 8 * (s & 1));
+    if (c >= rep) qf[s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  f32x4 sacc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      sacc[j] = mfma16(kv8_dec8(kreg[j][s >> 1][2 * (s & 1)], kreg[j][s >> 1][2 * (s & 1) + 1]), qf[s], sacc[j]);
+  }
+  // softmax over this wave's 64 keys, per head (= lane column c); lane (c, g)
+  // holds keys wk0 + 16 j + 4 g + i
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int key = wk0 + 16 * j + 4 * g + i;
+      const float x = key < k_hi ? sacc[j][i] * kscl[j][i] * sl : -INFINITY;
+      sacc[j][i] = x;
+      mx = fmaxf(mx, x);
+    }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  const float mref = mx == -INFINITY ? 0.f : mx;  // wave with no valid key: all p = 0
+  float ls = 0.f;
+  u16x8 pb[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float p = __builtin_amdgcn_exp2f(sacc[j][i] - mref);
+      ls += p;
+      pb[j >> 1][4 * (j & 1) + i] = f2bf(p);
+    }
+  ls += __shfl_xor(ls, 16, 64);
+  ls += __shfl_xor(ls, 32, 64);
+
+  // the wave's V image: bf16 rows of 256 B, 16-B chunks swizzled by dswz (rows past k_hi
+  // duplicate a valid row; their probabilities are exactly 0)
+#pragma unroll
+  for (int seg = 0; seg < 8; ++seg) {
+    const int row = seg * 8 + (lane >> 3), ch = 2 * (lane & 7);
+    char* dst = vs + row * ROWB;
+    *reinterpret_cast<u16x8*>(dst + 16 * (ch ^ dswz(row))) = kv8_dec8(vreg[seg][0], vreg[seg][1], vscl[seg]);
+    *reinterpret_cast<u16x8*>(dst + 16 * ((ch + 1) ^ dswz(row))) = kv8_dec8(vreg[seg][2], vreg[seg][3], vscl[seg]);
+  }
+  // O^T[d][head] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}.  Only this wave
+  // reads its image, and a wave's LDS operations complete in order.
+  f32x4 oacc[8];
+#pragma unroll
+  for (int db = 0; db < 8; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int qq = c >> 2, pp = c & 3;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int r0 = 32 * t + 4 * g + qq, r1 = r0 + 16;
+#pragma unroll
+    for (int db = 0; db < 8; ++db) {
+      const int ch = 2 * db + (pp >> 1);
+      const u16x4 va = tr_read16(vs + r0 * ROWB + 16 * (ch ^ dswz(r0)) + 8 * (pp & 1));
+      const u16x4 vb = tr_read16(vs + r1 * ROWB + 16 * (ch ^ dswz(r1)) + 8 * (pp & 1));
+      const u16x8 a = u16x8{va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
+      oacc[db] = mfma16(a, pb[t], oacc[db]);
+    }
+  }
+  // merge the four waves: each wave parks (m, l, O^T) in its own V region
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's transposed reads retired
+  float* so = reinterpret_cast<float*>(vs);  // [d][16 heads]
+#pragma unroll
+  for (int db = 0; db < 8; ++db)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) so[(16 * db + 4 * g + i) * 16 + c] = oacc[db][i];
+  if (g == 0) {
+    mls[w][0][c] = mx;
+    mls[w][1][c] = ls;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < rep * D; idx += 256) {
+    const int h = idx / D, d = idx % D;
+    float M = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) M = fmaxf(M, mls[ww][0][h]);
+    float L = 0.f, acc = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float mw = mls[ww][0][h];
+      const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
+      L += f * mls[ww][1][h];
+      acc += f * reinterpret_cast<const float*>(smem + ww * WTILE)[d * 16 + h];
+    }
+    part_o[(((int64_t)b * Hq + hk * rep + h) * nsplit + split) * D + d] = acc;
+    if (d == 0) {
+      pml[(int64_t)h * nsplit * 2] = M;
+      pml[(int64_t)h * nsplit * 2 + 1] = L;
+    }
+  }
+}
+
+// grid (nsplit, Hkv, B): the (m, l, o) partials of decode_attn_mfma_kernel over a kv8 cache,
+// merged by decode_combine_kernel
+__global__ void __launch_bounds__(256, 2) decode_attn_kv8_kernel(
+    const uint16_t* __restrict__ q, const uint8_t* __restrict__ kq, const float* __restrict__ ksc,
+    const uint8_t* __restrict__ vq, const float* __restrict__ vsc, const int32_t* __restrict__ lens, int len_off,
+    const int32_t* __restrict__ slots, float* __restrict__ part_ml, float* __restrict__ part_o, int Hq, int Hkv,
+    int max_seq, int nsplit, float sl, const int32_t* __restrict__ bt, int maxb) {
+  constexpr int WTILE = 64 * 256;  // 16 KiB per wave
+  __shared__ __attribute__((aligned(16))) char smem[4 * WTILE];
+  __shared__ float mls[4][2][16];
+  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int rep = Hq / Hkv;
+  const int len = lens[b] + len_off;
+  const int slot = slots ? slots[b] : b;
+  const int k_lo = split * kSplit;
+  const int k_hi = min(len, k_lo + kSplit);
+  const int tid = threadIdx.x;
+  float* pml = part_ml + (((int64_t)b * Hq + hk * rep) * nsplit + split) * 2;
+  if (k_lo >= k_hi) {  // empty split (workgroup-uniform): neutral partial
+    if (tid < rep) {
+      pml[(int64_t)tid * nsplit * 2] = -INFINITY;
+      pml[(int64_t)tid * nsplit * 2 + 1] = 0.f;
+    }
+    return;
+  }
+  decode_split_body_kv8(q, kq, ksc, vq, vsc, part_o, pml, smem, mls, b, hk, rep, Hq, split, nsplit, k_lo, k_hi, slot,
+                        max_seq, sl, bt, maxb, Hkv);
+}
+
 __device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
   h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
@@ -645,6 +948,43 @@ extern "C" int mx_decode_attn(const uint16_t* q, const uint16_t* kc, const uint1
   decode_combine_kernel<DD><<<B * Hq, DD, 0, stream>>>(part_ml, part_o, out, nsplit)
   if (D == 64) { DA(64); } else if (D == 32) { DA(32); } else return -1;
 #undef DA
+  return (int)hipGetLastError();
+}
+
+// x [R, 128] bf16 rows (stride ldx, a multiple of 8) -> codes [R, 128] u8, scales [R] f32
+extern "C" int mx_kv8_quant_rows(const uint16_t* x, int64_t ldx, uint8_t* q, float* s, int64_t R,
+                                 hipStream_t stream) {
+  if (R <= 0) return 0;
+  if (ldx % 8 || ldx < 128 || (R + 15) / 16 > 0x7fffffff) return -1;
+  kv8_quant_rows_kernel<<<(unsigned)((R + 15) / 16), 256, 0, stream>>>(x, ldx, q, s, R);
+  return (int)hipGetLastError();
+}
+
+// mx_rope_append into kv8 pools (codes kq / vq, scales ks / vs); head_dim 128
+extern "C" int mx_rope_append_kv8(const uint16_t* qkv, const float* cosb, const float* sinb, const int32_t* pos,
+                                  const int32_t* slots, uint16_t* q, uint8_t* kq, float* ks, uint8_t* vq, float* vs,
+                                  int B, int Hq, int Hkv, int max_seq, const int32_t* bt, int maxb,
+                                  hipStream_t stream) {
+  const int64_t items = (int64_t)B * (Hq + 2 * Hkv) * 8;
+  if (items <= 0) return 0;
+  if ((items + 255) / 256 > 0x7fffffff) return -1;
+  rope_append_kv8_kernel<<<(unsigned)((items + 255) / 256), 256, 0, stream>>>(qkv, cosb, sinb, pos, slots, q, kq, ks,
+                                                                              vq, vs, B, Hq, Hkv, max_seq, bt, maxb);
+  return (int)hipGetLastError();
+}
+
+// mx_decode_attn over kv8 pools; head_dim 128, always the combine kernel
+extern "C" int mx_decode_attn_kv8(const uint16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq,
+                                  const float* vs, const int32_t* lens, int len_off, const int32_t* slots,
+                                  float* part_ml, float* part_o, uint16_t* out, int B, int Hq, int Hkv, int max_seq,
+                                  int nsplit, float scale, const int32_t* bt, int maxb, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (Hq % Hkv || Hq / Hkv > kMaxRep || !out) return -1;
+  if (bt && max_seq % kSplit) return -1;  // a split must lie inside one block
+  dim3 grid(nsplit, Hkv, B);
+  decode_attn_kv8_kernel<<<grid, 256, 0, stream>>>(q, kq, ks, vq, vs, lens, len_off, slots, part_ml, part_o, Hq, Hkv,
+                                                   max_seq, nsplit, scale * 1.4426950408889634f, bt, maxb);
+  decode_combine_kernel<128><<<B * Hq, 128, 0, stream>>>(part_ml, part_o, out, nsplit);
   return (int)hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """Inference ops: prefill attention into a KV cache, decode attention, sampling.
 
-GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, greedy /
-Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature),
+GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, their kv8
+forms over an fp8 KV cache, greedy / Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature),
 logits_proc.hip (sampling penalties, logit_bias, log-probabilities) and
 attn_fwd.hip for prefill.  CPU: reference implementations.
 """
@@ -50,14 +50,106 @@ def _kv_at(cache: torch.Tensor, bt, slot: int, p0: int, p1: int) -> torch.Tensor
     return torch.cat(parts, 1)
 
 
+# ---------------------------------------------------------------- kv8: the fp8 (e4m3) KV cache
+# Row format and CPU codec: mxllm/serve/quant.py (kv8_quantize / kv8_dequantize).  Pools of one
+# layer: codes uint8 [rows, Hkv, SEQ, 128] and scales f32 [rows, Hkv, SEQ], for K and for V.
+def _kv8_codec():
+    from ..serve.quant import kv8_dequantize, kv8_quantize
+
+    return kv8_quantize, kv8_dequantize
+
+
+def kv8_quant_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """bf16 rows [R, 128] (row stride a multiple of 8) -> (codes uint8 [R, 128], scale f32 [R])."""
+    if use_native(x):
+        return native().kv8_quant_rows(x)
+    return _kv8_codec()[0](x)
+
+
+def _pool_rows(cache, bt, slots, pos):
+    """Index tensors (first index [B], row [B]) of position pos[b] of slots[b] (None: b)."""
+    B = pos.shape[0]
+    p = pos.long().cpu()
+    s = slots.long().cpu() if slots is not None else torch.arange(B)
+    if bt is None:
+        return s, p
+    blk = cache.shape[2]
+    return bt.cpu().long()[s, p // blk], p % blk
+
+
+def rope_append_kv8(qkv: torch.Tensor, cos, sin, pos, slots, k_codes, k_scale, v_codes, v_scale, Hq: int, Hkv: int,
+                    block_table: torch.Tensor | None = None) -> torch.Tensor:
+    """``rope_append`` into a kv8 cache: the K row rotated and rounded to bf16 as ``rope_append``
+    stores it, then K and V rows quantised (``kv8_quantize``) into the four pools at ``pos``.
+    Returns the rotated q [B, Hq, 128] bf16.  head_dim 128."""
+    if use_native(qkv):
+        return native().rope_append_kv8(qkv.contiguous(), cos, sin, pos, slots, k_codes, k_scale, v_codes, v_scale,
+                                        Hq, Hkv, block_table)
+    D = 128
+    if qkv.shape[1] != (Hq + 2 * Hkv) * D or k_codes.shape[-1] != D:
+        raise ValueError("rope_append_kv8: the fp8 KV cache supports head_dim 128 only")
+    quant = _kv8_codec()[0]
+    B = qkv.shape[0]
+    x = qkv.view(B, Hq + 2 * Hkv, D).float()
+    c, sn = cos[pos.long()].view(B, 1, D // 2), sin[pos.long()].view(B, 1, D // 2)
+
+    def rot(t):
+        t1, t2 = t[..., : D // 2], t[..., D // 2:]
+        return torch.cat([t1 * c - t2 * sn, t2 * c + t1 * sn], -1).to(qkv.dtype)
+
+    i0, r = _pool_rows(k_codes, block_table, slots, pos)
+    for codes, scale, rows in ((k_codes, k_scale, rot(x[:, Hq:Hq + Hkv])), (v_codes, v_scale, qkv.view(B, -1, D)[:, Hq + Hkv:])):
+        cd, sc = quant(rows)
+        codes[i0, :, r] = cd
+        scale[i0, :, r] = sc
+    return rot(x[:, :Hq])
+
+
+def decode_attn_kv8(q: torch.Tensor, k_codes, k_scale, v_codes, v_scale, lens, slots, max_len: int, scale: float,
+                    len_off: int = 0, block_table: torch.Tensor | None = None) -> torch.Tensor:
+    """``decode_attn`` over a kv8 cache: q [B, Hq, 128] bf16 attends over the first
+    ``lens[b] + len_off`` rows of slot ``slots[b]`` -> [B, Hq * 128] bf16.  The CPU path is the
+    fp32 softmax expression on the dequantised rows."""
+    if use_native(q):
+        return native().decode_attn_kv8(q, k_codes, k_scale, v_codes, v_scale, lens, slots, max_len, scale, len_off,
+                                        block_table)
+    if q.shape[-1] != 128 or k_codes.shape[-1] != 128:
+        raise ValueError("decode_attn_kv8: the fp8 KV cache supports head_dim 128 only")
+    deq = _kv8_codec()[1]
+    bt = block_table.cpu() if block_table is not None else None
+    B, Hq, D = q.shape
+    Hkv = k_codes.shape[1]
+    out = torch.zeros(B, Hq * D, dtype=q.dtype)
+    for i in range(B):
+        L, s = int(lens[i]) + len_off, int(slots[i]) if slots is not None else i
+        if L <= 0:
+            continue
+        kk = deq(_kv_at(k_codes, bt, s, 0, L), _kv_at(k_scale, bt, s, 0, L)).float().repeat_interleave(Hq // Hkv, 0)
+        vv = deq(_kv_at(v_codes, bt, s, 0, L), _kv_at(v_scale, bt, s, 0, L)).float().repeat_interleave(Hq // Hkv, 0)
+        sc = torch.einsum("hd,hld->hl", q[i].float(), kk) * scale
+        out[i] = torch.einsum("hl,hld->hd", sc.softmax(-1), vv).reshape(-1).to(q.dtype)
+    return out
+
+
 def decode_attention(qkv: torch.Tensor, cos, sin, k_cache, v_cache, pos: torch.Tensor, slots: torch.Tensor,
                      Hq: int, Hkv: int, D: int, max_len: int, block_table: torch.Tensor | None = None,
-                     counters: torch.Tensor | None = None) -> torch.Tensor:
+                     counters: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                     v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """Batched single-token step.  qkv [B, NH*D], pos/slots int32 [B] (pos = index
     of the new token).  Appends K/V at ``pos`` and attends over ``pos + 1`` keys.
     ``block_table`` [slots, max_blocks] int32: paged caches [blocks, Hkv, block, D].
     ``counters``: zeroed int32 [>= B * Hkv] owned by the caller — the split-K
-    partials then merge inside the attention launch (no combine kernel)."""
+    partials then merge inside the attention launch (no combine kernel).
+    ``k_scale`` / ``v_scale``: the caches are kv8 code pools with these scale pools (fp8 KV
+    cache, head_dim 128; ``counters`` is not used there)."""
+    if k_scale is not None or v_scale is not None:
+        if k_scale is None or v_scale is None:
+            raise ValueError("decode_attention: a kv8 cache needs both k_scale and v_scale")
+        if D != 128:
+            raise ValueError(f"decode_attention: the fp8 KV cache supports head_dim 128 only, got {D}")
+        q = rope_append_kv8(qkv, cos, sin, pos, slots, k_cache, k_scale, v_cache, v_scale, Hq, Hkv, block_table)
+        return decode_attn_kv8(q, k_cache, k_scale, v_cache, v_scale, pos, slots, max_len, 1.0 / math.sqrt(D), 1,
+                               block_table)
     if use_native(qkv):
         ops = native()
         q = ops.rope_append(qkv.contiguous(), cos, sin, pos, slots, k_cache, v_cache, Hq, Hkv, D, block_table)

@@ -147,13 +147,19 @@ class Request:
 class Engine:
     def __init__(self, model, max_batch: int = 8, max_seq: int = 4096, device=None, eos_ids=(),
                  use_graphs: bool | None = None, prefill_tokens: int = 16384, tp_group=None,
-                 kv_pool_tokens: int | None = None, kv_block: int = 256):
+                 kv_pool_tokens: int | None = None, kv_block: int = 256, kv_dtype: str | None = None):
         """``tp_group``: serve a tensor-parallel shard (mxllm/parallel/tensor.py
         ``shard_llama`` / ``random_shard``) with the other ranks of the group;
         every rank of the group runs the same schedule (same submissions in the
         same order, e.g. SPMD ``generate`` or ``serve_follower``).
         ``kv_pool_tokens``: paged KV cache of that many tokens shared by all slots
-        (None: every slot owns max_seq positions; env MXLLM_KV_POOL_TOKENS)."""
+        (None: every slot owns max_seq positions; env MXLLM_KV_POOL_TOKENS).
+        ``kv_dtype``: "bf16" or "fp8" (None: env MXLLM_KV_CACHE, default bf16).  fp8 stores the
+        cache as e4m3 codes with one power-of-two scale per (token, KV head) row
+        (mxllm/serve/kvcache.py; head_dim 128): prefill attends over the fresh bf16 K/V and only
+        the cache write quantises; a decode step runs RMSNorm + QKV GEMM + ``rope_append_kv8`` +
+        ``decode_attn_kv8`` (the fused QKV epilogue cannot see a whole row's amax, so
+        MXLLM_ROPE_FUSED, MXLLM_DECODE_COMBINE=fused and MXLLM_MERGE_FUSED do not apply)."""
         self.model = model
         self.tp = None
         if tp_group is not None:
@@ -189,17 +195,25 @@ class Engine:
         n_slots = max_batch + (1 if self.use_graphs else 0)
         if kv_pool_tokens is None and os.environ.get("MXLLM_KV_POOL_TOKENS"):
             kv_pool_tokens = int(os.environ["MXLLM_KV_POOL_TOKENS"])
-        from .kvcache import KVCache
+        from .kvcache import KV_DTYPES, KVCache
 
+        if kv_dtype is None:
+            kv_dtype = os.environ.get("MXLLM_KV_CACHE") or "bf16"
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype / MXLLM_KV_CACHE must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        if kv_dtype == "fp8" and c.head_dim != 128:
+            raise ValueError(f"the fp8 KV cache supports head_dim 128 only; this model has head_dim {c.head_dim}")
+        self.kv_dtype = kv_dtype
         self.kv = KVCache(c.n_layers, c.n_kv_heads, c.head_dim, dt, self.device, n_slots, self.max_seq,
                           pool_tokens=kv_pool_tokens, block=kv_block,
-                          scratch_slot=self.scratch_slot if self.use_graphs else None)
+                          scratch_slot=self.scratch_slot if self.use_graphs else None, kv_dtype=kv_dtype)
         # MXLLM_DECODE_COMBINE=fused: the split-K partials merge inside the attention launch (the
         # last workgroup of each (seq, kv-head) combines; these counters stay zero between calls)
         # instead of the combine kernel -- measured slower in the graphed step at every batch
         # (archive/profiles/r3g/README.md), so off by default
         self._attn_cnt = None
-        if self.device.type == "cuda" and os.environ.get("MXLLM_DECODE_COMBINE", "kernel") == "fused":
+        if (self.device.type == "cuda" and not self.kv.fp8
+                and os.environ.get("MXLLM_DECODE_COMBINE", "kernel") == "fused"):
             self._attn_cnt = torch.zeros((n_slots + 64) * self.kv.k[0].shape[1], dtype=torch.int32,
                                          device=self.device)
         self._pf_stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" and _PREFETCH else None
@@ -392,7 +406,8 @@ class Engine:
         bt = self.kv.bt
         B = inp.shape[1]
         nsplit = (min(max_len, self.kv.maxb * self.kv.block) + 255) // 256
-        merge = _MERGE_FUSED and c.head_dim == 128 and B <= 4 and nsplit <= 16
+        fp8 = self.kv.fp8
+        merge = _MERGE_FUSED and not fp8 and c.head_dim == 128 and B <= 4 and nsplit <= 16
         cnt = self._attn_cnt
         if cnt is not None and B * self.kv.k[0].shape[1] > cnt.numel():
             cnt = None
@@ -424,13 +439,18 @@ class Engine:
                                                              1.0 / math.sqrt(c.head_dim), 1, bt)
                 return ops.native().decode_attn(q, self.kv.k[i], self.kv.v[i], pos, sl, max_len,
                                                 1.0 / math.sqrt(c.head_dim), 1, bt, cnt)
+            if fp8:
+                return dops.decode_attention(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], pos, sl,
+                                             c.n_heads, c.n_kv_heads, c.head_dim, max_len, bt,
+                                             k_scale=self.kv.k_scale[i], v_scale=self.kv.v_scale[i])
             return dops.decode_attention(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], pos, sl,
                                          c.n_heads, c.n_kv_heads, c.head_dim, max_len, bt, cnt)
 
         def qkv_fn(i, delta, h, gamma, layer):
             # QKV GEMM with the RoPE/cache-append epilogue; 1-2 rows also with the RMSNorm prologue
             # (one launch), more rows after the RMSNorm kernel
-            if not (_ROPE_FUSED and self.tp is None and c.head_dim == 128
+            # (not into an fp8 cache: a row's amax spans the workgroups of that epilogue)
+            if not (_ROPE_FUSED and not fp8 and self.tp is None and c.head_dim == 128
                     and type(layer.wqkv) is FusedLinear and layer.wqkv.lora_r == 0):
                 return None
             rope = (layer.wqkv.weight, m.rope_cos, m.rope_sin, pos, sl, self.kv.k[i], self.kv.v[i],
@@ -562,7 +582,7 @@ class Engine:
                 "mean_ttft_s": self.ttft_sum / n, "mean_latency_s": self.latency_sum / n,
                 "prefill_tokens_per_s": self.prefill_tokens / self.prefill_s if self.prefill_s else 0.0,
                 "decode_tokens_per_s": self.decode_tokens / self.decode_s if self.decode_s else 0.0,
-                "decode_steps": self.steps}
+                "decode_steps": self.steps, "kv_cache_dtype": self.kv_dtype, "kv_cache_bytes": self.kv.nbytes()}
 
     def _finish(self, r: Request, reason: str):
         r.finish_reason = reason

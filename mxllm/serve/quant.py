@@ -64,6 +64,37 @@ def dequantize_e4m3(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return v * scale.float()[:, None]
 
 
+# ---------------------------------------------------------------- kv8: the fp8 KV-cache row format
+# A row is the 128 values of one (token, KV head).  scale = 2^e, the smallest power of two with
+# amax(|row|) / scale <= 448, so amax / scale lies in (224, 448]: with amax = m * 2^E (1 <= m < 2),
+# e = E - 8 if m <= 1.75 else E - 7, clamped to >= -100; an all-zero row has scale 1.
+# code = e4m3fn(x / scale), round to nearest even, true zero and subnormals kept (unlike the weight
+# format above).  The scale is a power of two, so x / scale is exact and code * scale is a bf16
+# value: the dequantised cache is a bf16 cache.  Inputs are finite.  The HIP kernels
+# (csrc/kernels/decode.hip kv8_*) produce the same bits; this is their reference and the CPU path.
+KV8_DIM = 128
+KV8_MIN_EXP = -100
+
+
+def kv8_quantize(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [..., 128] bf16 -> (codes uint8 [..., 128], scale f32 [...])."""
+    if x.dtype != torch.bfloat16 or x.shape[-1] != KV8_DIM:
+        raise ValueError(f"kv8_quantize: bf16 rows of {KV8_DIM} values, got {x.dtype} {tuple(x.shape)}")
+    xf = x.float()
+    bits = xf.abs().amax(-1).view(torch.int32)
+    e = (bits >> 23) - 135 + ((bits & 0x7FFFFF) > 0x600000).to(torch.int32)
+    e = torch.where(bits == 0, torch.zeros_like(e), e.clamp_min(KV8_MIN_EXP))
+    scale = ((e + 127) << 23).view(torch.float32)
+    inv = ((127 - e) << 23).view(torch.float32)
+    codes = (xf * inv.unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), scale.contiguous()
+
+
+def kv8_dequantize(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [..., 128], scale f32 [...] -> bf16 [..., 128] (exact: see above)."""
+    return (codes.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)).to(torch.bfloat16)
+
+
 class W8Linear(nn.Module):
     """Frozen projection y = x W^T with fp8 weights (serving only)."""
 

@@ -152,7 +152,9 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
                  f"mxllm_prefill_tokens_total {engine.prefill_tokens}",
                  f"mxllm_prefill_seconds_total {engine.prefill_s:.6f}",
                  f"mxllm_decode_tokens_total {engine.decode_tokens}",
-                 f"mxllm_decode_seconds_total {engine.decode_s:.6f}"]
+                 f"mxllm_decode_seconds_total {engine.decode_s:.6f}",
+                 f'mxllm_kv_cache_info{{kv_cache_dtype="{engine.kv_dtype}"}} 1',
+                 f"mxllm_kv_cache_bytes {engine.kv.nbytes()}"]
         return PlainTextResponse("\n".join(lines) + "\n")
 
     @app.post("/v1/chat/completions")
@@ -285,10 +287,11 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
 
 def build_default(model: str = "tiny", device: str | None = None, max_batch: int = 8, max_seq: int = 2048,
                   checkpoint: str | None = None, tokenizer_path: str | None = None, seed: int = 0,
-                  weights: str = "bf16", tp_group=None):
+                  weights: str = "bf16", tp_group=None, kv_cache: str | None = None):
     """Engine + tokenizer.  ``tp_group``: this rank serves its tensor-parallel
     shard (mxllm/parallel/tensor.py) of the model; the full model is built (or
-    loaded) on the rank's GPU, sliced and freed."""
+    loaded) on the rank's GPU, sliced and freed.  ``kv_cache``: "bf16" / "fp8" KV cache
+    (None: env MXLLM_KV_CACHE, default bf16; ``Engine(kv_dtype=...)``)."""
     from ..data.tokenizer import get_tokenizer
     from ..models import build_model, tokenizer_path_for
 
@@ -317,11 +320,11 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
         quantize_model_fp8_(m)
     tok = get_tokenizer(cfg.vocab_size, tokenizer_path, cfg.bos_id, cfg.eos_id)
     eng = Engine(m, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id, getattr(tok, "eos_id", cfg.eos_id)),
-                 tp_group=tp_group)
+                 tp_group=tp_group, kv_dtype=kv_cache)
     return eng, tok
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default=os.environ.get("MXLLM_MODEL", "tiny"),
                     help="preset name, or a Hugging Face Llama directory (config.json + safetensors + tokenizer.json)")
@@ -338,7 +341,14 @@ def main(argv=None):
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree: launch with torchrun --nproc-per-node=TP; rank 0 serves HTTP, "
                          "the other ranks follow its schedule")
-    a = ap.parse_args(argv)
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default=os.environ.get("MXLLM_KV_CACHE") or "bf16",
+                    help="fp8: e4m3 KV cache, one byte per element and one f32 scale per (token, KV head) row "
+                         "(head_dim 128; mxllm/serve/kvcache.py)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     group, env = None, None
     if a.tp > 1:
@@ -351,7 +361,7 @@ def main(argv=None):
             raise SystemExit(f"--tp {a.tp} needs exactly {a.tp} ranks (torchrun --nproc-per-node={a.tp})")
         group = dist.group.WORLD
     eng, tok = build_default(a.model, None, a.max_batch, a.max_seq, a.checkpoint, a.tokenizer, weights=a.weights,
-                             tp_group=group)
+                             tp_group=group, kv_cache=a.kv_cache)
     if group is not None:
         eng.enable_tp_sync()
         if env.rank != 0:
