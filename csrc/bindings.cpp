@@ -857,83 +857,125 @@ static KvPages kv_pages(const c10::optional<at::Tensor>& block_table, const at::
   return pg;
 }
 
-// qkv [B, NH*D]; k_cache/v_cache [slots, Hkv, max_seq, D] (or paged); pos/slots int32 [B]
-at::Tensor rope_append(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
-                       const c10::optional<at::Tensor>& slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                       int64_t Hkv, int64_t D, const c10::optional<at::Tensor>& block_table) {
-  check_bf16(qkv, "qkv");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
-  MX_CHECK(pos.scalar_type() == at::kInt, "pos int32");
-  const int64_t B = qkv.size(0);
-  MX_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width");
-  MX_CHECK(k_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == D, "cache shape");
-  DevGuard g(qkv.device());
-  const int32_t* sl = nullptr;
-  if (slots.has_value()) sl = slots->data_ptr<int32_t>();
-  auto q = at::empty({B, Hq, D}, qkv.options());
-  const KvPages pg = kv_pages(block_table, k_cache);
-  MX_OK(mx_rope_append(bf(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int32_t>(), sl, bfm(q),
-                       bfm(k_cache), bfm(v_cache), (int)B, (int)Hq, (int)Hkv, (int)D, (int)k_cache.size(2), pg.bt,
-                       pg.maxb, cur_stream()));
-  return q;
+// Operand checks of the decode ops, bf16 and kv8 caches alike.  Every check runs before anything is
+// allocated or written.
+//
+// K and V pools of one layer: [rows, Hkv, SEQ, D] of one element type, equal in shape
+static void check_kv_pools(const at::Tensor& k, const at::Tensor& v, at::ScalarType dt, int64_t D,
+                           const at::Device& dev, int64_t Hkv, const char* op) {
+  for (const at::Tensor* c : {&k, &v})
+    MX_CHECK(c->device() == dev && c->scalar_type() == dt && c->is_contiguous() && c->dim() == 4, op,
+             ": K and V pools must be contiguous ", c10::toString(dt), " [rows, Hkv, SEQ, D] on the query's device");
+  MX_CHECK(k.size(3) == D, op, ": the pools' last dimension is ", k.size(3), ", expected head_dim ", D);
+  MX_CHECK(k.size(1) == Hkv, op, ": the pools hold ", k.size(1), " KV heads, expected ", Hkv);
+  MX_CHECK(v.sizes() == k.sizes(), op, ": the K and V pools differ in shape");
 }
-
-at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& lens, const c10::optional<at::Tensor>& slots, int64_t max_len, double scale,
-                       int64_t len_off, const c10::optional<at::Tensor>& block_table,
-                       const c10::optional<at::Tensor>& counters) {
-  check_bf16(q, "q");
-  MX_CHECK(lens.scalar_type() == at::kInt, "lens int32");
-  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
-  const int64_t Hkv = k_cache.size(1), max_seq = k_cache.size(2);
-  DevGuard g(q.device());
-  // counters: int32 [>= B * Hkv], zero, owned by the caller (a decode engine): the split
-  // partials are merged in-launch by the last workgroup of each (seq, kv-head), which
-  // resets its counter -> no combine launch (head_dim 128)
-  unsigned int* cnt = nullptr;
-  if (counters.has_value() && D == 128) {
-    MX_CHECK(counters->scalar_type() == at::kInt && counters->is_contiguous() && counters->numel() >= B * Hkv &&
-                 counters->device() == q.device(),
-             "decode_attn: counters must be a contiguous int32 tensor of >= B * Hkv zeros on q's device");
-    cnt = reinterpret_cast<unsigned int*>(counters->data_ptr<int32_t>());
-  }
-  const KvPages pg = kv_pages(block_table, k_cache);
-  const int64_t cap = pg.bt ? (int64_t)pg.maxb * max_seq : max_seq;  // positions a sequence can hold
-  const int64_t nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);
-  auto ml = at::empty({B, Hq, nsplit, 2}, q.options().dtype(at::kFloat));
-  auto po = at::empty({B, Hq, nsplit, D}, q.options().dtype(at::kFloat));
-  auto out = at::empty({B, Hq * D}, q.options());
-  const int32_t* sl = nullptr;
-  if (slots.has_value()) sl = slots->data_ptr<int32_t>();
-  MX_OK(mx_decode_attn(bf(q), bf(k_cache), bf(v_cache), lens.data_ptr<int32_t>(), (int)len_off, sl, ml.data_ptr<float>(),
-                       po.data_ptr<float>(), bfm(out), (int)B, (int)Hq, (int)Hkv, (int)D, (int)max_seq, (int)nsplit,
-                       (float)scale, pg.bt, pg.maxb, cnt, cur_stream()));
-  return out;
-}
-
-// ---------------------------------------------------------------- kv8: fp8 (e4m3) KV cache, head_dim 128
-// Pools of one layer: codes uint8 [rows, Hkv, SEQ, 128] and scales f32 [rows, Hkv, SEQ] for K and
-// for V (contiguous or paged like the bf16 caches).  Every check runs before anything is written.
-static void check_kv8_pools(const at::Tensor& k_codes, const at::Tensor& k_scale, const at::Tensor& v_codes,
-                            const at::Tensor& v_scale, const at::Device& dev, int64_t Hkv, const char* op) {
-  for (const at::Tensor* c : {&k_codes, &v_codes})
-    MX_CHECK(c->device() == dev && c->scalar_type() == at::kByte && c->is_contiguous() && c->dim() == 4, op,
-             ": code pools must be contiguous uint8 [rows, Hkv, SEQ, 128] on the query's device");
-  MX_CHECK(k_codes.size(3) == 128, op, ": the fp8 KV cache supports head_dim 128 only, got ", k_codes.size(3));
-  MX_CHECK(k_codes.size(1) == Hkv, op, ": code pools hold ", k_codes.size(1), " KV heads, expected ", Hkv);
-  MX_CHECK(v_codes.sizes() == k_codes.sizes(), op, ": k_codes and v_codes differ in shape");
-  for (const at::Tensor* s : {&k_scale, &v_scale})
-    MX_CHECK(s->device() == dev && s->scalar_type() == at::kFloat && s->is_contiguous() && s->dim() == 3 &&
-                 s->size(0) == k_codes.size(0) && s->size(1) == Hkv && s->size(2) == k_codes.size(2),
-             op, ": scale pools must be contiguous float32 [rows, Hkv, SEQ] matching the code pools");
-}
+// lens / pos / slots: one int32 per sequence (nullptr for an optional tensor that is not given)
 static const int32_t* check_rows_i32(const c10::optional<at::Tensor>& t, const at::Device& dev, int64_t B,
                                      const char* op, const char* name) {
   if (!t.has_value() || !t->defined()) return nullptr;
   MX_CHECK(t->device() == dev && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == B, op, ": ", name,
            " must be a contiguous int32 [B] tensor on the query's device");
   return t->data_ptr<int32_t>();
+}
+static void check_gqa(int64_t Hq, int64_t Hkv, const char* op) {
+  MX_CHECK(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, op, ": ", Hq, " q-heads over ", Hkv,
+           " KV heads: the group size must be a whole number of at most 16");
+}
+
+// The split plan of a decode-attention call: one split per 256 positions that a sequence of at
+// most max_len tokens can hold, and the partials (m, l) [B, Hq, nsplit, 2], o [B, Hq, nsplit, D]
+struct DecodeSplits {
+  int64_t nsplit;
+  at::Tensor ml, po;
+};
+static DecodeSplits decode_splits(const at::Tensor& q, int64_t max_seq, int64_t max_len, const KvPages& pg) {
+  const int64_t cap = pg.bt ? (int64_t)pg.maxb * max_seq : max_seq;  // positions a sequence can hold
+  const int64_t nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);
+  const auto f32 = q.options().dtype(at::kFloat);
+  return {nsplit, at::empty({q.size(0), q.size(1), nsplit, 2}, f32),
+          at::empty({q.size(0), q.size(1), nsplit, q.size(2)}, f32)};
+}
+
+// qkv [B, NH*D]; k_cache/v_cache [slots, Hkv, max_seq, D] (or paged); pos/slots int32 [B]
+at::Tensor rope_append(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                       const c10::optional<at::Tensor>& slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
+                       int64_t Hkv, int64_t D, const c10::optional<at::Tensor>& block_table) {
+  check_bf16(qkv, "qkv");
+  MX_CHECK(qkv.dim() == 2 && Hq > 0 && Hkv > 0 && qkv.size(1) == (Hq + 2 * Hkv) * D,
+           "rope_append: qkv must be [B, (Hq + 2 Hkv) * D]");
+  const int64_t B = qkv.size(0);
+  check_kv_pools(k_cache, v_cache, at::kBFloat16, D, qkv.device(), Hkv, "rope_append");
+  MX_CHECK(pos.defined(), "rope_append: pos");
+  const int32_t* pp = check_rows_i32(pos, qkv.device(), B, "rope_append", "pos");
+  const int32_t* sl = check_rows_i32(slots, qkv.device(), B, "rope_append", "slots");
+  DevGuard g(qkv.device());
+  const KvPages pg = kv_pages(block_table, k_cache);
+  auto q = at::empty({B, Hq, D}, qkv.options());
+  MX_OK(mx_rope_append(bf(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), pp, sl, bfm(q), bfm(k_cache),
+                       bfm(v_cache), (int)B, (int)Hq, (int)Hkv, (int)D, (int)k_cache.size(2), pg.bt, pg.maxb,
+                       cur_stream()));
+  return q;
+}
+
+// The operand checks of decode_attn and decode_attn_partials (op: the caller's name) and what the
+// launch takes from the operands
+struct DecodeCall {
+  int64_t B, Hq, Hkv, D, max_seq;
+  const int32_t *lens, *slots;
+  KvPages pg;
+};
+static DecodeCall check_decode_attn(const char* op, const at::Tensor& q, const at::Tensor& k_cache,
+                                    const at::Tensor& v_cache, const at::Tensor& lens,
+                                    const c10::optional<at::Tensor>& slots,
+                                    const c10::optional<at::Tensor>& block_table) {
+  check_bf16(q, "q");
+  MX_CHECK(q.dim() == 3, op, ": q must be [B, Hq, D]");
+  MX_CHECK(k_cache.dim() == 4, op, ": the caches must be bf16 [rows, Hkv, SEQ, D]");
+  DecodeCall c{q.size(0), q.size(1), k_cache.size(1), q.size(2), k_cache.size(2), nullptr, nullptr, {}};
+  check_kv_pools(k_cache, v_cache, at::kBFloat16, c.D, q.device(), c.Hkv, op);
+  check_gqa(c.Hq, c.Hkv, op);
+  MX_CHECK(lens.defined(), op, ": lens");
+  c.lens = check_rows_i32(lens, q.device(), c.B, op, "lens");
+  c.slots = check_rows_i32(slots, q.device(), c.B, op, "slots");
+  c.pg = kv_pages(block_table, k_cache);
+  return c;
+}
+
+at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& lens, const c10::optional<at::Tensor>& slots, int64_t max_len, double scale,
+                       int64_t len_off, const c10::optional<at::Tensor>& block_table,
+                       const c10::optional<at::Tensor>& counters) {
+  const DecodeCall c = check_decode_attn("decode_attn", q, k_cache, v_cache, lens, slots, block_table);
+  // counters: int32 [>= B * Hkv], zero, owned by the caller (a decode engine): the split
+  // partials are merged in-launch by the last workgroup of each (seq, kv-head), which
+  // resets its counter -> no combine launch (head_dim 128)
+  unsigned int* cnt = nullptr;
+  if (counters.has_value() && c.D == 128) {
+    MX_CHECK(counters->scalar_type() == at::kInt && counters->is_contiguous() && counters->numel() >= c.B * c.Hkv &&
+                 counters->device() == q.device(),
+             "decode_attn: counters must be a contiguous int32 tensor of >= B * Hkv zeros on q's device");
+    cnt = reinterpret_cast<unsigned int*>(counters->data_ptr<int32_t>());
+  }
+  DevGuard g(q.device());
+  DecodeSplits sp = decode_splits(q, c.max_seq, max_len, c.pg);
+  auto out = at::empty({c.B, c.Hq * c.D}, q.options());
+  MX_OK(mx_decode_attn(bf(q), bf(k_cache), bf(v_cache), c.lens, (int)len_off, c.slots, sp.ml.data_ptr<float>(),
+                       sp.po.data_ptr<float>(), bfm(out), (int)c.B, (int)c.Hq, (int)c.Hkv, (int)c.D, (int)c.max_seq,
+                       (int)sp.nsplit, (float)scale, c.pg.bt, c.pg.maxb, cnt, cur_stream()));
+  return out;
+}
+
+// ---------------------------------------------------------------- kv8: fp8 (e4m3) KV cache, head_dim 128
+// Pools of one layer: codes uint8 [rows, Hkv, SEQ, 128] and scales f32 [rows, Hkv, SEQ] for K and
+// for V (contiguous or paged like the bf16 caches).
+static void check_kv8_pools(const at::Tensor& k_codes, const at::Tensor& k_scale, const at::Tensor& v_codes,
+                            const at::Tensor& v_scale, const at::Device& dev, int64_t Hkv, const char* op) {
+  check_kv_pools(k_codes, v_codes, at::kByte, 128, dev, Hkv, op);
+  for (const at::Tensor* s : {&k_scale, &v_scale})
+    MX_CHECK(s->device() == dev && s->scalar_type() == at::kFloat && s->is_contiguous() && s->dim() == 3 &&
+                 s->size(0) == k_codes.size(0) && s->size(1) == Hkv && s->size(2) == k_codes.size(2),
+             op, ": scale pools must be contiguous float32 [rows, Hkv, SEQ] matching the code pools");
 }
 
 // x [R, 128] bf16 rows (row stride a multiple of 8) -> (codes uint8 [R, 128], scale f32 [R])
@@ -988,22 +1030,18 @@ at::Tensor decode_attn_kv8(const at::Tensor& q, const at::Tensor& k_codes, const
   MX_CHECK(k_codes.dim() == 4, "decode_attn_kv8: code pools must be uint8 [rows, Hkv, SEQ, 128]");
   const int64_t Hkv = k_codes.size(1), max_seq = k_codes.size(2);
   check_kv8_pools(k_codes, k_scale, v_codes, v_scale, q.device(), Hkv, "decode_attn_kv8");
-  MX_CHECK(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, "decode_attn_kv8: ", Hq, " q-heads over ", Hkv,
-           " KV heads: the group size must be a whole number of at most 16");
+  check_gqa(Hq, Hkv, "decode_attn_kv8");
   MX_CHECK(lens.defined(), "decode_attn_kv8: lens");
   const int32_t* lp = check_rows_i32(lens, q.device(), B, "decode_attn_kv8", "lens");
   const int32_t* sl = check_rows_i32(slots, q.device(), B, "decode_attn_kv8", "slots");
   DevGuard g(q.device());
   const KvPages pg = kv_pages(block_table, k_codes);
-  const int64_t cap = pg.bt ? (int64_t)pg.maxb * max_seq : max_seq;  // positions a sequence can hold
-  const int64_t nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);
-  auto ml = at::empty({B, Hq, nsplit, 2}, q.options().dtype(at::kFloat));
-  auto po = at::empty({B, Hq, nsplit, 128}, q.options().dtype(at::kFloat));
+  DecodeSplits sp = decode_splits(q, max_seq, max_len, pg);
   auto out = at::empty({B, Hq * 128}, q.options());
   MX_OK(mx_decode_attn_kv8(bf(q), k_codes.data_ptr<uint8_t>(), k_scale.data_ptr<float>(), v_codes.data_ptr<uint8_t>(),
-                           v_scale.data_ptr<float>(), lp, (int)len_off, sl, ml.data_ptr<float>(), po.data_ptr<float>(),
-                           bfm(out), (int)B, (int)Hq, (int)Hkv, (int)max_seq, (int)nsplit, (float)scale, pg.bt, pg.maxb,
-                           cur_stream()));
+                           v_scale.data_ptr<float>(), lp, (int)len_off, sl, sp.ml.data_ptr<float>(),
+                           sp.po.data_ptr<float>(), bfm(out), (int)B, (int)Hq, (int)Hkv, (int)max_seq, (int)sp.nsplit,
+                           (float)scale, pg.bt, pg.maxb, cur_stream()));
   return out;
 }
 
@@ -1014,23 +1052,14 @@ std::tuple<at::Tensor, at::Tensor> decode_attn_partials(const at::Tensor& q, con
                                                         const c10::optional<at::Tensor>& slots, int64_t max_len,
                                                         double scale, int64_t len_off,
                                                         const c10::optional<at::Tensor>& block_table) {
-  check_bf16(q, "q");
-  MX_CHECK(lens.scalar_type() == at::kInt, "lens int32");
-  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
-  MX_CHECK(D == 128, "decode_attn_partials: head_dim 128");
-  const int64_t Hkv = k_cache.size(1), max_seq = k_cache.size(2);
+  const DecodeCall c = check_decode_attn("decode_attn_partials", q, k_cache, v_cache, lens, slots, block_table);
+  MX_CHECK(c.D == 128, "decode_attn_partials: head_dim 128");
   DevGuard g(q.device());
-  const KvPages pg = kv_pages(block_table, k_cache);
-  const int64_t cap = pg.bt ? (int64_t)pg.maxb * max_seq : max_seq;
-  const int64_t nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);
-  auto ml = at::empty({B, Hq, nsplit, 2}, q.options().dtype(at::kFloat));
-  auto po = at::empty({B, Hq, nsplit, D}, q.options().dtype(at::kFloat));
-  const int32_t* sl = nullptr;
-  if (slots.has_value()) sl = slots->data_ptr<int32_t>();
-  MX_OK(mx_decode_attn(bf(q), bf(k_cache), bf(v_cache), lens.data_ptr<int32_t>(), (int)len_off, sl, ml.data_ptr<float>(),
-                       po.data_ptr<float>(), nullptr, (int)B, (int)Hq, (int)Hkv, (int)D, (int)max_seq, (int)nsplit,
-                       (float)scale, pg.bt, pg.maxb, nullptr, cur_stream()));
-  return {ml, po};
+  DecodeSplits sp = decode_splits(q, c.max_seq, max_len, c.pg);
+  MX_OK(mx_decode_attn(bf(q), bf(k_cache), bf(v_cache), c.lens, (int)len_off, c.slots, sp.ml.data_ptr<float>(),
+                       sp.po.data_ptr<float>(), nullptr, (int)c.B, (int)c.Hq, (int)c.Hkv, (int)c.D, (int)c.max_seq,
+                       (int)sp.nsplit, (float)scale, c.pg.bt, c.pg.maxb, nullptr, cur_stream()));
+  return {sp.ml, sp.po};
 }
 
 // y [M, N] = merge(part_ml, part_o) . W^T (decode o-projection with the split merge in the prologue)

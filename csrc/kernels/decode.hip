@@ -19,6 +19,38 @@
 
 namespace mx {
 
+// Item i of a rope_append launch over qkv [B, NH * D]: D / 16 items per (row b, head), each with
+// the value chunks c and c + D / 2 (8 values each) of a rotation pair
+template <int D>
+struct RopeItem {
+  static constexpr int HALF = D / 2, CPH = HALF / 8;
+  int b, head, c, p, slot;
+  u16x8 x1, x2;
+  __device__ __forceinline__ RopeItem(int64_t i, const uint16_t* __restrict__ qkv, const int32_t* __restrict__ pos,
+                                      const int32_t* __restrict__ slots, int NH) {
+    c = (int)(i % CPH) * 8;
+    head = (int)((i / CPH) % NH);
+    b = (int)(i / ((int64_t)CPH * NH));
+    p = pos[b];
+    slot = slots ? slots[b] : b;
+    const uint16_t* src = qkv + (int64_t)b * NH * D + (int64_t)head * D;
+    x1 = *reinterpret_cast<const u16x8*>(src + c);
+    x2 = *reinterpret_cast<const u16x8*>(src + HALF + c);
+  }
+  // (x1, x2) rotated by the angles of position p
+  __device__ __forceinline__ void rotate(const float* __restrict__ cosb, const float* __restrict__ sinb, u16x8& y1,
+                                         u16x8& y2) const {
+    const float* cp = cosb + (int64_t)p * HALF + c;
+    const float* sp = sinb + (int64_t)p * HALF + c;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float a = bf2f(x1[j]), bb = bf2f(x2[j]);
+      y1[j] = f2bf(a * cp[j] - bb * sp[j]);
+      y2[j] = f2bf(bb * cp[j] + a * sp[j]);
+    }
+  }
+};
+
 // qkv [B, (Hq+2Hkv)*D] -> q [B, Hq, D] (rotated), K/V cache rows at pos[b]
 template <int D>
 __global__ void __launch_bounds__(256) rope_append_kernel(const uint16_t* __restrict__ qkv,
@@ -33,33 +65,19 @@ __global__ void __launch_bounds__(256) rope_append_kernel(const uint16_t* __rest
   const int NH = Hq + 2 * Hkv;
   const int64_t n = (int64_t)B * NH * CPH;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int cc = (int)(i % CPH);
-    const int head = (int)((i / CPH) % NH);
-    const int b = (int)(i / ((int64_t)CPH * NH));
-    const int c = cc * 8;
-    const int p = pos[b];
-    const int slot = slots ? slots[b] : b;
-    const uint16_t* src = qkv + (int64_t)b * NH * D + (int64_t)head * D;
-    u16x8 x1 = *reinterpret_cast<const u16x8*>(src + c);
-    u16x8 x2 = *reinterpret_cast<const u16x8*>(src + HALF + c);
+    const RopeItem<D> it(i, qkv, pos, slots, NH);
+    const int head = it.head, c = it.c;
     uint16_t* dst;
     if (head >= Hq + Hkv) {
-      dst = vc + kv_row(bt, maxb, max_seq, slot, Hkv, head - Hq - Hkv, p) * D;
-      *reinterpret_cast<u16x8*>(dst + c) = x1;
-      *reinterpret_cast<u16x8*>(dst + HALF + c) = x2;
+      dst = vc + kv_row(bt, maxb, max_seq, it.slot, Hkv, head - Hq - Hkv, it.p) * D;
+      *reinterpret_cast<u16x8*>(dst + c) = it.x1;
+      *reinterpret_cast<u16x8*>(dst + HALF + c) = it.x2;
       continue;
     }
-    dst = head < Hq ? q + ((int64_t)b * Hq + head) * D
-                    : kc + kv_row(bt, maxb, max_seq, slot, Hkv, head - Hq, p) * D;
-    const float* cp = cosb + (int64_t)p * HALF + c;
-    const float* sp = sinb + (int64_t)p * HALF + c;
+    dst = head < Hq ? q + ((int64_t)it.b * Hq + head) * D
+                    : kc + kv_row(bt, maxb, max_seq, it.slot, Hkv, head - Hq, it.p) * D;
     u16x8 y1, y2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float a = bf2f(x1[j]), bb = bf2f(x2[j]);
-      y1[j] = f2bf(a * cp[j] - bb * sp[j]);
-      y2[j] = f2bf(bb * cp[j] + a * sp[j]);
-    }
+    it.rotate(cosb, sinb, y1, y2);
     *reinterpret_cast<u16x8*>(dst + c) = y1;
     *reinterpret_cast<u16x8*>(dst + HALF + c) = y2;
   }
@@ -67,6 +85,51 @@ __global__ void __launch_bounds__(256) rope_append_kernel(const uint16_t* __rest
 
 constexpr int kSplit = 256;  // keys per workgroup
 constexpr int kMaxRep = 16;  // q-heads per kv-head supported
+
+// stores / loads of the split partials that another workgroup of the SAME launch merges:
+// write-through (sc1, relaxed agent-scope atomic store), so no release fence (an L2
+// write-back per workgroup) is needed, and loads that bypass this CU's L1 (guide
+// §6 Guideline 16, the sc1 hand-off form)
+// st: 0 = plain store, 1 = agent-scope relaxed atomic store (sc1 write-through),
+// 2 = system-scope relaxed atomic store; ld: 0 = plain load, 1 = agent, 2 = system
+__device__ __forceinline__ void st_part(float* p, float v, int st) {
+  if (st == 1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if (st == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  else *p = v;
+}
+__device__ __forceinline__ float ld_part(const float* p, int ld) {
+  float* q = const_cast<float*>(p);
+  if (ld == 1) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ld == 2) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return *p;
+}
+
+// The work of one workgroup of a decode-attention grid (nsplit, Hkv, B): keys k_lo .. k_hi - 1 of
+// cache slot `slot`, kv-head hk, for the rep q-heads of its GQA group.  pml: the group's first
+// head's (m, l) of this split; head h at + h * nsplit * 2.
+struct DecodeSplit {
+  int split, hk, b, rep, slot, k_lo, k_hi;
+  float* pml;
+};
+// false for an empty split (workgroup-uniform), whose neutral partial is stored here (mode st)
+__device__ __forceinline__ bool decode_split_begin(DecodeSplit& s, const int32_t* __restrict__ lens, int len_off,
+                                                   const int32_t* __restrict__ slots, float* __restrict__ part_ml,
+                                                   int Hq, int Hkv, int nsplit, int st) {
+  s.split = blockIdx.x, s.hk = blockIdx.y, s.b = blockIdx.z;
+  s.rep = Hq / Hkv;
+  const int len = lens[s.b] + len_off;
+  s.slot = slots ? slots[s.b] : s.b;
+  s.k_lo = s.split * kSplit;
+  s.k_hi = min(len, s.k_lo + kSplit);
+  s.pml = part_ml + (((int64_t)s.b * Hq + s.hk * s.rep) * nsplit + s.split) * 2;
+  if (s.k_lo < s.k_hi) return true;
+  const int tid = threadIdx.x;
+  if (tid < s.rep) {
+    st_part(&s.pml[(int64_t)tid * nsplit * 2], -INFINITY, st);
+    st_part(&s.pml[(int64_t)tid * nsplit * 2 + 1], 0.f, st);
+  }
+  return false;
+}
 
 // grid (nsplit, Hkv, B); block 256 = one key per thread for the score phase.
 template <int D>
@@ -82,21 +145,11 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
   __shared__ float ps[kMaxRep][kSplit];
   __shared__ float red[kMaxRep][4];
   __shared__ __attribute__((aligned(16))) uint16_t vs[kSplit * D];
-  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const int rep = Hq / Hkv;
-  const int len = lens[b] + len_off;
-  const int slot = slots ? slots[b] : b;
-  const int k_lo = split * kSplit;
-  const int k_hi = min(len, k_lo + kSplit);
+  DecodeSplit ds;
+  if (!decode_split_begin(ds, lens, len_off, slots, part_ml, Hq, Hkv, nsplit, 0)) return;
+  const int split = ds.split, hk = ds.hk, b = ds.b, rep = ds.rep, slot = ds.slot, k_lo = ds.k_lo, k_hi = ds.k_hi;
+  float* pml = ds.pml;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  float* pml = part_ml + (((int64_t)b * Hq + hk * rep) * nsplit + split) * 2;
-  if (k_lo >= k_hi) {  // empty split: neutral partial
-    if (tid < rep) {
-      pml[(int64_t)tid * nsplit * 2] = -INFINITY;
-      pml[(int64_t)tid * nsplit * 2 + 1] = 0.f;
-    }
-    return;
-  }
   for (int i = tid; i < rep * D; i += 256) {
     const int h = i / D, d = i % D;
     qs[h][d] = bf2f(q[((int64_t)b * Hq + hk * rep + h) * D + d]);
@@ -206,6 +259,9 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
 //     decode_combine_kernel.
 // 64 KiB LDS and < 128 VGPRs: two workgroups (8 waves) per CU, 256 KiB of K/V
 // in flight per CU.
+// decode_split_body is a template over the cache format: how K and V reach the
+// fragments and the image above is KvBf16's; KvFp8 (kv8 section) decodes e4m3
+// codes on the way.  Everything from the softmax on exists once.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((address_space(1))) const void* gptr_t;
@@ -224,77 +280,95 @@ __device__ __forceinline__ u16x4 tr_read16(const char* p) {
 // 16-B chunk swizzle of a 256-B row (conflict-free row and transposed reads)
 __device__ __forceinline__ int dswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-// stores / loads of the split partials that another workgroup of the SAME launch merges:
-// write-through (sc1, relaxed agent-scope atomic store), so no release fence (an L2
-// write-back per workgroup) is needed, and loads that bypass this CU's L1 (guide
-// §6 Guideline 16, the sc1 hand-off form)
-// st: 0 = plain store, 1 = agent-scope relaxed atomic store (sc1 write-through),
-// 2 = system-scope relaxed atomic store; ld: 0 = plain load, 1 = agent, 2 = system
-__device__ __forceinline__ void st_part(float* p, float v, int st) {
-  if (st == 1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else if (st == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else *p = v;
-}
-__device__ __forceinline__ float ld_part(const float* p, int ld) {
-  float* q = const_cast<float*>(p);
-  if (ld == 1) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (ld == 2) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  return *p;
-}
+// What decode_split_body needs from a cache format (this one and KvFp8 below).  rb + key is the
+// cache row of every key of the split (kv_row: a split lies in one block); lane = (c, g) = (lane &
+// 15, lane >> 4); the wave's keys are wk0 .. wk0 + 63 and its 16-KiB LDS region is vs.  Keys at or
+// past k_hi are never loaded: the index is clamped to k_hi - 1.
+//   * load_v: issues the loads of the wave's V rows; finish_v: the swizzled bf16 V image (rows of
+//     256 B, 16-B chunks permuted by dswz) is complete in vs.  Rows past k_hi duplicate a valid
+//     row (finite; their probabilities are exactly 0);
+//   * load_k: issues the loads of the K operands; k_frag(j, s): the A fragment of block j, k-step s,
+//     K[wk0 + 16 j + c][q_col(s, g) .. +7];
+//   * q_col(s, g): the first of the 8 dimensions that k-step s covers for lane group g (the MFMA
+//     summation order of the format);
+//   * score(x, j, i): x times the format's factor for key wk0 + 16 j + 4 g + i;
+//   * kQFirst: Q is loaded before K (the order of the loads as each format was tuned).
+//
+// bf16 cache: K rows go straight from HBM into the A fragments (16 B per lane), V rows to LDS by
+// LDS-DMA (16 x 1-KiB lane-linear pieces; swizzle by permuting each lane's SOURCE chunk).
+struct KvBf16 {
+  static constexpr bool kQFirst = true;
+  const uint16_t* kc;
+  const uint16_t* vc;
+  u16x8 kf[4][4];
+  __device__ __forceinline__ void load_v(int64_t rb, int wk0, int k_hi, int lane, char* vs) {
+    const uint16_t* vbase = vc + rb * 128;
+#pragma unroll
+    for (int seg = 0; seg < 16; ++seg) {
+      const int row = seg * 4 + (lane >> 4), slt = lane & 15;
+      const int ch = slt ^ dswz(row);
+      const int key = min(wk0 + row, k_hi - 1);
+      __builtin_amdgcn_global_load_lds((gptr_t)(vbase + (int64_t)key * 128 + ch * 8), (lptr_t)(vs + seg * 1024), 16,
+                                       0, 0);
+    }
+  }
+  __device__ __forceinline__ void finish_v(int, char*) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's V DMA has landed (only it reads vs)
+  }
+  __device__ __forceinline__ void load_k(int64_t rb, int wk0, int k_hi, int c, int g) {
+    const uint16_t* kbase = kc + rb * 128;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = min(wk0 + 16 * j + c, k_hi - 1);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) kf[j][s] = *reinterpret_cast<const u16x8*>(kbase + (int64_t)key * 128 + q_col(s, g));
+    }
+  }
+  __device__ __forceinline__ u16x8 k_frag(int j, int s) const { return kf[j][s]; }
+  static __device__ __forceinline__ int q_col(int s, int g) { return 32 * s + 8 * g; }
+  __device__ __forceinline__ float score(float x, int, int) const { return x; }
+};
 
-// one split of decode_attn_mfma_kernel: (m, l, o) partial of 256 keys for every
-// q-head of the GQA group (see the kernel's header comment)
-__device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
-                                                  const uint16_t* __restrict__ vc, float* __restrict__ part_o,
-                                                  float* __restrict__ pml, char* smem, float (*mls)[2][16], int b,
-                                                  int hk, int rep, int Hq, int split, int nsplit, int k_lo, int k_hi,
-                                                  int slot, int max_seq, float sl, const int32_t* __restrict__ bt,
-                                                  int maxb, int Hkv, int st) {
+// one split of a decode-attention kernel over a cache of format KV: (m, l, o) partial of 256 keys
+// for every q-head of the GQA group (see the header comment above), stored in mode st
+template <class KV>
+__device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q, KV& kv, float* __restrict__ part_o,
+                                                  const DecodeSplit& ds, char* smem, float (*mls)[2][16], int Hq,
+                                                  int Hkv, int nsplit, int max_seq, float sl,
+                                                  const int32_t* __restrict__ bt, int maxb, int st) {
   constexpr int D = 128, ROWB = 256, WKEYS = 64, WTILE = WKEYS * ROWB;
+  const int b = ds.b, hk = ds.hk, rep = ds.rep, split = ds.split, k_lo = ds.k_lo, k_hi = ds.k_hi;
+  float* pml = ds.pml;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
-  const int64_t kvb = (kv_row(bt, maxb, max_seq, slot, Hkv, hk, k_lo) - k_lo) * D;  // one block per split
-  const uint16_t* kbase = kc + kvb;
-  const uint16_t* vbase = vc + kvb;
+  const int64_t rb = kv_row(bt, maxb, max_seq, ds.slot, Hkv, hk, k_lo) - k_lo;  // one block per split
   const int wk0 = k_lo + WKEYS * w;
   char* vs = smem + w * WTILE;
 
-  // V rows of this wave -> LDS (16 x 1-KiB lane-linear DMA pieces; swizzle by
-  // permuting each lane's SOURCE chunk).  Rows past k_hi duplicate a valid row
-  // (finite; their probabilities are exactly 0).
-#pragma unroll
-  for (int seg = 0; seg < 16; ++seg) {
-    const int row = seg * 4 + (lane >> 4), slt = lane & 15;
-    const int ch = slt ^ dswz(row);
-    const int key = min(wk0 + row, k_hi - 1);
-    __builtin_amdgcn_global_load_lds((gptr_t)(vbase + (int64_t)key * D + ch * 8), (lptr_t)(vs + seg * 1024), 16, 0,
-                                     0);
-  }
-  // Q^T fragments (B operand): lane (c, g) holds Q[head c][32 s + 8 g .. +7]
+  kv.load_v(rb, wk0, k_hi, lane, vs);
+  if constexpr (!KV::kQFirst) kv.load_k(rb, wk0, k_hi, c, g);
+  // Q^T fragments (B operand): lane (c, g), k-step s holds Q[head c][q_col(s, g) .. +7]
   u16x8 qf[4];
   const uint16_t* qrow = q + ((int64_t)b * Hq + hk * rep + min(c, rep - 1)) * D;
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    qf[s] = *reinterpret_cast<const u16x8*>(qrow + 32 * s + 8 * g);
+    qf[s] = *reinterpret_cast<const u16x8*>(qrow + KV::q_col(s, g));
     if (c >= rep) qf[s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
-  // K fragments (A operand), straight from HBM: block j, k-step s ->
-  // K[wk0 + 16 j + c][32 s + 8 g .. +7]
-  u16x8 kf[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int key = min(wk0 + 16 * j + c, k_hi - 1);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) kf[j][s] = *reinterpret_cast<const u16x8*>(kbase + (int64_t)key * D + 32 * s + 8 * g);
-  }
+  if constexpr (KV::kQFirst) kv.load_k(rb, wk0, k_hi, c, g);
   f32x4 sacc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < 4; ++s) sacc[j] = mfma16(kf[j][s], qf[s], sacc[j]);
+    for (int s = 0; s < 4; ++s) sacc[j] = mfma16(kv.k_frag(j, s), qf[s], sacc[j]);
   }
+  // Nothing is scheduled across this point, so every load of the split is in flight before the
+  // softmax.  Loads to here and softmax are one basic block, and without the barrier the scheduler
+  // sinks two of KvFp8's V loads (and their scales) to just before finish_v, where nothing hides
+  // their latency.
+  __builtin_amdgcn_sched_barrier(0);
   // softmax over this wave's 64 keys, per head (= lane column c); lane (c, g)
   // holds keys wk0 + 16 j + 4 g + i
   float mx = -INFINITY;
@@ -303,7 +377,7 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int key = wk0 + 16 * j + 4 * g + i;
-      const float x = key < k_hi ? sacc[j][i] * sl : -INFINITY;
+      const float x = key < k_hi ? kv.score(sacc[j][i], j, i) * sl : -INFINITY;
       sacc[j][i] = x;
       mx = fmaxf(mx, x);
     }
@@ -323,11 +397,12 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
   ls += __shfl_xor(ls, 16, 64);
   ls += __shfl_xor(ls, 32, 64);
 
-  // O^T[d][head] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}
+  // O^T[d][head] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}.  Only this wave
+  // reads its image, and a wave's LDS operations complete in order.
   f32x4 oacc[8];
 #pragma unroll
   for (int db = 0; db < 8; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's V DMA has landed (only it reads vs)
+  kv.finish_v(lane, vs);
   const int qq = c >> 2, pp = c & 3;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -374,6 +449,24 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
   }
 }
 
+// One output value from its nsplit partials, ml = (m, l) pairs and po = o values D floats apart,
+// loaded in mode LD (ld_part): the maximum over the splits, then weights, L and acc in split order.
+// The in-launch merger and decode_combine_kernel both use it, so they agree bit for bit.
+template <int LD>
+__device__ __forceinline__ float merge_splits(const float* ml, const float* po, int nsplit, int D) {
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ld_part(ml + 2 * s, LD));
+  float L = 0.f, acc = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float m = ld_part(ml + 2 * s, LD);
+    if (m == -INFINITY) continue;
+    const float wgt = __builtin_amdgcn_exp2f(m - M);
+    L += wgt * ld_part(ml + 2 * s + 1, LD);
+    acc += wgt * ld_part(po + (int64_t)s * D, LD);
+  }
+  return L > 0.f ? acc / L : 0.f;
+}
+
 // proto (fused split merge, cnt != nullptr; 0 = partials only / combine kernel):
 //   1 = partials stored with agent-scope (sc1, write-through) atomic stores, read back with
 //       agent-scope atomic loads, no fences;
@@ -396,26 +489,16 @@ __global__ void __launch_bounds__(256, 2) decode_attn_mfma_kernel(const uint16_t
   __shared__ __attribute__((aligned(16))) char smem[4 * WTILE];
   __shared__ float mls[4][2][16];
   __shared__ int s_last;
-  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const int rep = Hq / Hkv;
-  const int len = lens[b] + len_off;
-  const int slot = slots ? slots[b] : b;
-  const int k_lo = split * kSplit;
-  const int k_hi = min(len, k_lo + kSplit);
   const int tid = threadIdx.x;
   const bool fused = cnt != nullptr;
   const int st = !fused ? 0 : proto == 2 ? 2 : proto == 4 ? 0 : 1;  // store mode of the partials
-  float* pml = part_ml + (((int64_t)b * Hq + hk * rep) * nsplit + split) * 2;
-  if (k_lo >= k_hi) {  // empty split (workgroup-uniform): neutral partial
-    if (tid < rep) {
-      st_part(&pml[(int64_t)tid * nsplit * 2], -INFINITY, st);
-      st_part(&pml[(int64_t)tid * nsplit * 2 + 1], 0.f, st);
-    }
-  } else {
-    decode_split_body(q, kc, vc, part_o, pml, smem, mls, b, hk, rep, Hq, split, nsplit, k_lo, k_hi, slot, max_seq,
-                      sl, bt, maxb, Hkv, st);
+  DecodeSplit ds;
+  if (decode_split_begin(ds, lens, len_off, slots, part_ml, Hq, Hkv, nsplit, st)) {
+    KvBf16 kv{kc, vc};
+    decode_split_body(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, st);
   }
   if (!fused) return;
+  const int hk = ds.hk, b = ds.b, rep = ds.rep;
   // In-launch combine: the last of the nsplit workgroups of this (seq, kv-head) to arrive
   // merges the partials and resets the counter (zero again for the next call).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its partial stores done
@@ -440,23 +523,15 @@ __global__ void __launch_bounds__(256, 2) decode_attn_mfma_kernel(const uint16_t
   }
   __syncthreads();
   if (!s_last) return;
-  const int ld = proto == 1 ? 1 : proto == 2 ? 2 : 0;
-  // the same arithmetic, in the same order, as decode_combine_kernel
   for (int idx = tid; idx < rep * D; idx += 256) {
     const int h = idx / D, d = idx % D;
     const int64_t bh = (int64_t)b * Hq + hk * rep + h;
     const float* ml = part_ml + bh * nsplit * 2;
-    float M = -INFINITY;
-    for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, ld_part(ml + 2 * sp, ld));
-    float L = 0.f, acc = 0.f;
-    for (int sp = 0; sp < nsplit; ++sp) {
-      const float m = ld_part(ml + 2 * sp, ld);
-      if (m == -INFINITY) continue;
-      const float wgt = __builtin_amdgcn_exp2f(m - M);
-      L += wgt * ld_part(ml + 2 * sp + 1, ld);
-      acc += wgt * ld_part(part_o + (bh * nsplit + sp) * D + d, ld);
-    }
-    out[bh * D + d] = f2bf(L > 0.f ? acc / L : 0.f);
+    const float* po = part_o + bh * nsplit * D + d;
+    const float o = proto == 1 ? merge_splits<1>(ml, po, nsplit, D)
+                  : proto == 2 ? merge_splits<2>(ml, po, nsplit, D)
+                               : merge_splits<0>(ml, po, nsplit, D);
+    out[bh * D + d] = f2bf(o);
   }
 }
 
@@ -470,7 +545,7 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
   const int d = threadIdx.x;
   if (nsplit <= 8) {
     // every partial load issued at once (one memory round trip instead of two: the outputs'
-    // loads do not wait for the maxima); same arithmetic order as the loop below
+    // loads do not wait for the maxima); same arithmetic order as merge_splits
     float mv[8], lv[8], ov[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -493,17 +568,7 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
     out[bh * D + d] = f2bf(L > 0.f ? acc / L : 0.f);
     return;
   }
-  float M = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[2 * s]);
-  float L = 0.f, acc = 0.f;
-  for (int s = 0; s < nsplit; ++s) {
-    const float m = ml[2 * s];
-    if (m == -INFINITY) continue;
-    const float wgt = __builtin_amdgcn_exp2f(m - M);
-    L += wgt * ml[2 * s + 1];
-    acc += wgt * part_o[(bh * nsplit + s) * D + d];
-  }
-  out[bh * D + d] = f2bf(L > 0.f ? acc / L : 0.f);
+  out[bh * D + d] = f2bf(merge_splits<0>(ml, part_o + bh * nsplit * D + d, nsplit, D));
 }
 
 // ---------------------------------------------------------------------------
@@ -588,28 +653,12 @@ __global__ void __launch_bounds__(256) rope_append_kv8_kernel(
   const int NH = Hq + 2 * Hkv;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)B * NH * CPH) return;  // whole 8-lane groups leave
-  const int cc = (int)(i % CPH);
-  const int head = (int)((i / CPH) % NH);
-  const int b = (int)(i / ((int64_t)CPH * NH));
-  const int c = cc * 8;
-  const int p = pos[b];
-  const int slot = slots ? slots[b] : b;
-  const uint16_t* src = qkv + (int64_t)b * NH * D + (int64_t)head * D;
-  const u16x8 x1 = *reinterpret_cast<const u16x8*>(src + c);
-  const u16x8 x2 = *reinterpret_cast<const u16x8*>(src + HALF + c);
-  u16x8 y1 = x1, y2 = x2;
-  if (head < Hq + Hkv) {
-    const float* cp = cosb + (int64_t)p * HALF + c;
-    const float* sp = sinb + (int64_t)p * HALF + c;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float a = bf2f(x1[j]), bb = bf2f(x2[j]);
-      y1[j] = f2bf(a * cp[j] - bb * sp[j]);
-      y2[j] = f2bf(bb * cp[j] + a * sp[j]);
-    }
-  }
+  const RopeItem<D> it(i, qkv, pos, slots, NH);
+  const int head = it.head, c = it.c;
+  u16x8 y1 = it.x1, y2 = it.x2;
+  if (head < Hq + Hkv) it.rotate(cosb, sinb, y1, y2);
   if (head < Hq) {
-    uint16_t* dst = q + ((int64_t)b * Hq + head) * D;
+    uint16_t* dst = q + ((int64_t)it.b * Hq + head) * D;
     *reinterpret_cast<u16x8*>(dst + c) = y1;
     *reinterpret_cast<u16x8*>(dst + HALF + c) = y2;
     return;
@@ -620,15 +669,14 @@ __global__ void __launch_bounds__(256) rope_append_kv8_kernel(
   const int e = kv8_exp(am);
   const float inv = kv8_pow2(-e);
   const bool isv = head >= Hq + Hkv;
-  const int64_t r = kv_row(bt, maxb, max_seq, slot, Hkv, head - Hq - (isv ? Hkv : 0), p);
+  const int64_t r = kv_row(bt, maxb, max_seq, it.slot, Hkv, head - Hq - (isv ? Hkv : 0), it.p);
   uint8_t* dst = (isv ? vq : kq) + r * D;
   *reinterpret_cast<uint2*>(dst + c) = kv8_pack8(y1, inv);
   *reinterpret_cast<uint2*>(dst + HALF + c) = kv8_pack8(y2, inv);
-  if (cc == 0) (isv ? vs : ks)[r] = kv8_pow2(e);
+  if (c == 0) (isv ? vs : ks)[r] = kv8_pow2(e);
 }
 
-// decode_split_body over a kv8 cache: the same partition (256 keys per workgroup, 64 per wave),
-// MFMAs, softmax, V image and wave merge.  What differs:
+// kv8 cache for decode_split_body (the interface: KvBf16).  What differs from the bf16 cache:
 //   * K codes go from HBM into registers, 16 per lane and load: lane (c, g) holds
 //     K[key][64 sp + 16 g .. +15]; k-step s = 2 sp + h takes its bytes 8 h .. 8 h + 7, decoded to
 //     bf16 in registers, and the Q^T fragment of that k-step holds the same 8 dimensions;
@@ -638,145 +686,52 @@ __global__ void __launch_bounds__(256) rope_append_kv8_kernel(
 //     multiplied by the row's V scale and written to the swizzled bf16 image that the
 //     transposed reads expect.
 // Keys at or past k_hi are never loaded, codes or scales: the index is clamped to k_hi - 1.
-__device__ __forceinline__ void decode_split_body_kv8(
-    const uint16_t* __restrict__ q, const uint8_t* __restrict__ kq, const float* __restrict__ ksc,
-    const uint8_t* __restrict__ vq, const float* __restrict__ vsc, float* __restrict__ part_o, float* __restrict__ pml,
-    char* smem, float (*mls)[2][16], int b, int hk, int rep, int Hq, int split, int nsplit, int k_lo, int k_hi,
-    int slot, int max_seq, float sl, const int32_t* __restrict__ bt, int maxb, int Hkv) {
-  constexpr int D = 128, ROWB = 256, WKEYS = 64, WTILE = WKEYS * ROWB;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
-  const int64_t rb = kv_row(bt, maxb, max_seq, slot, Hkv, hk, k_lo) - k_lo;  // rb + key: every key of this split
-  const uint8_t* kbase = kq + rb * D;
-  const uint8_t* vbase = vq + rb * D;
-  const float* ksb = ksc + rb;
-  const float* vsb = vsc + rb;
-  const int wk0 = k_lo + WKEYS * w;
-  char* vs = smem + w * WTILE;
-
-  u32x4 vreg[8];
-  float vscl[8];
+struct KvFp8 {
+  static constexpr bool kQFirst = false;
+  const uint8_t* kq;
+  const float* ksc;
+  const uint8_t* vq;
+  const float* vsc;
+  u32x4 vreg[8], kreg[4][2];
+  float vscl[8], kscl[4][4];
+  __device__ __forceinline__ void load_v(int64_t rb, int wk0, int k_hi, int lane, char*) {
+    const uint8_t* vbase = vq + rb * 128;
+    const float* vsb = vsc + rb;
 #pragma unroll
-  for (int seg = 0; seg < 8; ++seg) {
-    const int key = min(wk0 + seg * 8 + (lane >> 3), k_hi - 1);
-    vreg[seg] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * D + 16 * (lane & 7));
-    vscl[seg] = vsb[key];
-  }
-  u32x4 kreg[4][2];
-  float kscl[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int key = min(wk0 + 16 * j + c, k_hi - 1);
-#pragma unroll
-    for (int sp = 0; sp < 2; ++sp)
-      kreg[j][sp] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)key * D + 64 * sp + 16 * g);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) kscl[j][i] = ksb[min(wk0 + 16 * j + 4 * g + i, k_hi - 1)];
-  }
-  // Q^T fragments (B operand): lane (c, g), k-step s = 2 sp + h holds Q[head c][64 sp + 16 g + 8 h .. +7]
-  u16x8 qf[4];
-  const uint16_t* qrow = q + ((int64_t)b * Hq + hk * rep + min(c, rep - 1)) * D;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    qf[s] = *reinterpret_cast<const u16x8*>(qrow + 64 * (s >> 1) + 16 * g + 8 * (s & 1));
-    if (c >= rep) qf[s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
-  f32x4 sacc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-      sacc[j] = mfma16(kv8_dec8(kreg[j][s >> 1][2 * (s & 1)], kreg[j][s >> 1][2 * (s & 1) + 1]), qf[s], sacc[j]);
-  }
-  // softmax over this wave's 64 keys, per head (= lane column c); lane (c, g)
-  // holds keys wk0 + 16 j + 4 g + i
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int key = wk0 + 16 * j + 4 * g + i;
-      const float x = key < k_hi ? sacc[j][i] * kscl[j][i] * sl : -INFINITY;
-      sacc[j][i] = x;
-      mx = fmaxf(mx, x);
-    }
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float mref = mx == -INFINITY ? 0.f : mx;  // wave with no valid key: all p = 0
-  float ls = 0.f;
-  u16x8 pb[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float p = __builtin_amdgcn_exp2f(sacc[j][i] - mref);
-      ls += p;
-      pb[j >> 1][4 * (j & 1) + i] = f2bf(p);
-    }
-  ls += __shfl_xor(ls, 16, 64);
-  ls += __shfl_xor(ls, 32, 64);
-
-  // the wave's V image: bf16 rows of 256 B, 16-B chunks swizzled by dswz (rows past k_hi
-  // duplicate a valid row; their probabilities are exactly 0)
-#pragma unroll
-  for (int seg = 0; seg < 8; ++seg) {
-    const int row = seg * 8 + (lane >> 3), ch = 2 * (lane & 7);
-    char* dst = vs + row * ROWB;
-    *reinterpret_cast<u16x8*>(dst + 16 * (ch ^ dswz(row))) = kv8_dec8(vreg[seg][0], vreg[seg][1], vscl[seg]);
-    *reinterpret_cast<u16x8*>(dst + 16 * ((ch + 1) ^ dswz(row))) = kv8_dec8(vreg[seg][2], vreg[seg][3], vscl[seg]);
-  }
-  // O^T[d][head] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}.  Only this wave
-  // reads its image, and a wave's LDS operations complete in order.
-  f32x4 oacc[8];
-#pragma unroll
-  for (int db = 0; db < 8; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int qq = c >> 2, pp = c & 3;
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int r0 = 32 * t + 4 * g + qq, r1 = r0 + 16;
-#pragma unroll
-    for (int db = 0; db < 8; ++db) {
-      const int ch = 2 * db + (pp >> 1);
-      const u16x4 va = tr_read16(vs + r0 * ROWB + 16 * (ch ^ dswz(r0)) + 8 * (pp & 1));
-      const u16x4 vb = tr_read16(vs + r1 * ROWB + 16 * (ch ^ dswz(r1)) + 8 * (pp & 1));
-      const u16x8 a = u16x8{va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-      oacc[db] = mfma16(a, pb[t], oacc[db]);
+    for (int seg = 0; seg < 8; ++seg) {
+      const int key = min(wk0 + seg * 8 + (lane >> 3), k_hi - 1);
+      vreg[seg] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * 128 + 16 * (lane & 7));
+      vscl[seg] = vsb[key];
     }
   }
-  // merge the four waves: each wave parks (m, l, O^T) in its own V region
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's transposed reads retired
-  float* so = reinterpret_cast<float*>(vs);  // [d][16 heads]
+  __device__ __forceinline__ void finish_v(int lane, char* vs) {
 #pragma unroll
-  for (int db = 0; db < 8; ++db)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) so[(16 * db + 4 * g + i) * 16 + c] = oacc[db][i];
-  if (g == 0) {
-    mls[w][0][c] = mx;
-    mls[w][1][c] = ls;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < rep * D; idx += 256) {
-    const int h = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) M = fmaxf(M, mls[ww][0][h]);
-    float L = 0.f, acc = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) {
-      const float mw = mls[ww][0][h];
-      const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-      L += f * mls[ww][1][h];
-      acc += f * reinterpret_cast<const float*>(smem + ww * WTILE)[d * 16 + h];
-    }
-    part_o[(((int64_t)b * Hq + hk * rep + h) * nsplit + split) * D + d] = acc;
-    if (d == 0) {
-      pml[(int64_t)h * nsplit * 2] = M;
-      pml[(int64_t)h * nsplit * 2 + 1] = L;
+    for (int seg = 0; seg < 8; ++seg) {
+      const int row = seg * 8 + (lane >> 3), ch = 2 * (lane & 7);
+      char* dst = vs + row * 256;
+      *reinterpret_cast<u16x8*>(dst + 16 * (ch ^ dswz(row))) = kv8_dec8(vreg[seg][0], vreg[seg][1], vscl[seg]);
+      *reinterpret_cast<u16x8*>(dst + 16 * ((ch + 1) ^ dswz(row))) = kv8_dec8(vreg[seg][2], vreg[seg][3], vscl[seg]);
     }
   }
-}
+  __device__ __forceinline__ void load_k(int64_t rb, int wk0, int k_hi, int c, int g) {
+    const uint8_t* kbase = kq + rb * 128;
+    const float* ksb = ksc + rb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = min(wk0 + 16 * j + c, k_hi - 1);
+#pragma unroll
+      for (int sp = 0; sp < 2; ++sp)
+        kreg[j][sp] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)key * 128 + 64 * sp + 16 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) kscl[j][i] = ksb[min(wk0 + 16 * j + 4 * g + i, k_hi - 1)];
+    }
+  }
+  __device__ __forceinline__ u16x8 k_frag(int j, int s) const {
+    return kv8_dec8(kreg[j][s >> 1][2 * (s & 1)], kreg[j][s >> 1][2 * (s & 1) + 1]);
+  }
+  static __device__ __forceinline__ int q_col(int s, int g) { return 64 * (s >> 1) + 16 * g + 8 * (s & 1); }
+  __device__ __forceinline__ float score(float x, int j, int i) const { return x * kscl[j][i]; }
+};
 
 // grid (nsplit, Hkv, B): the (m, l, o) partials of decode_attn_mfma_kernel over a kv8 cache,
 // merged by decode_combine_kernel
@@ -788,23 +743,10 @@ __global__ void __launch_bounds__(256, 2) decode_attn_kv8_kernel(
   constexpr int WTILE = 64 * 256;  // 16 KiB per wave
   __shared__ __attribute__((aligned(16))) char smem[4 * WTILE];
   __shared__ float mls[4][2][16];
-  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const int rep = Hq / Hkv;
-  const int len = lens[b] + len_off;
-  const int slot = slots ? slots[b] : b;
-  const int k_lo = split * kSplit;
-  const int k_hi = min(len, k_lo + kSplit);
-  const int tid = threadIdx.x;
-  float* pml = part_ml + (((int64_t)b * Hq + hk * rep) * nsplit + split) * 2;
-  if (k_lo >= k_hi) {  // empty split (workgroup-uniform): neutral partial
-    if (tid < rep) {
-      pml[(int64_t)tid * nsplit * 2] = -INFINITY;
-      pml[(int64_t)tid * nsplit * 2 + 1] = 0.f;
-    }
-    return;
-  }
-  decode_split_body_kv8(q, kq, ksc, vq, vsc, part_o, pml, smem, mls, b, hk, rep, Hq, split, nsplit, k_lo, k_hi, slot,
-                        max_seq, sl, bt, maxb, Hkv);
+  DecodeSplit ds;
+  if (!decode_split_begin(ds, lens, len_off, slots, part_ml, Hq, Hkv, nsplit, 0)) return;
+  KvFp8 kv{kq, ksc, vq, vsc};
+  decode_split_body(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, 0);
 }
 
 __device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) {

@@ -311,6 +311,52 @@ def test_decode_attn_refusals(gpu):
     check_refused(_ops(), gpu)
 
 
+def test_decode_layout_refusals(gpu):
+    """Operands of the wrong layout or type are refused by rope_append, decode_attn and decode_attn_partials
+    before anything is written.  Every refused tensor is one whose misreading would stay inside its own
+    storage (the 64-wide caches are cut from buffers of the full size)."""
+    ops, g = _ops(), _gen(7)
+    B, Hq, Hkv, D, S = 2, 8, 2, 128, 300
+    q = torch.randn(B, Hq, D, generator=g).to(BF16).to(gpu)
+    qkv = torch.randn(B, (Hq + 2 * Hkv) * D, generator=g).to(BF16).to(gpu)
+    cos, sin = (t.to(gpu) for t in ref.rope_tables(S, D, ROPE_THETA, None))
+
+    def cache(rows=S, width=D):
+        return torch.randn(2, Hkv, rows, width, generator=g).to(BF16).to(gpu)
+
+    def cache64():
+        return cache().view(-1)[:2 * Hkv * S * 64].view(2, Hkv, S, 64)
+
+    good = dict(rows=torch.tensor([5, 299], dtype=I32, device=gpu), slots=torch.tensor([1, 0], dtype=I32, device=gpu),
+                kc=cache(), vc=cache())
+    bad = {
+        "rows as a stride-2 view": dict(rows=torch.tensor([5, 7, 299, 9], dtype=I32, device=gpu)[::2]),
+        "slots with B + 1 elements": dict(slots=torch.tensor([1, 0, 1], dtype=I32, device=gpu)),
+        "int64 slots": dict(slots=good["slots"].long()),
+        "fp16 k_cache": dict(kc=good["kc"].to(torch.float16)),
+        "v_cache with more rows": dict(vc=cache(rows=S + 1)),
+        "non-contiguous k_cache": dict(kc=cache(width=D + 64)[:, :, :, :D]),
+        "caches 64 wide under a 128-wide q": dict(kc=cache64(), vc=cache64()),
+    }
+    calls = {
+        "rope_append": lambda a: ops.rope_append(qkv, cos, sin, a["rows"], a["slots"], a["kc"], a["vc"], Hq, Hkv, D, None),
+        "decode_attn": lambda a: ops.decode_attn(q, a["kc"], a["vc"], a["rows"], a["slots"], S, 1.0, 0, None, None),
+        "decode_attn_partials": lambda a: ops.decode_attn_partials(q, a["kc"], a["vc"], a["rows"], a["slots"], S, 1.0,
+                                                                   0, None),
+    }
+    for call in calls.values():  # the accepted form of the calls below
+        call(good)
+    for what, change in bad.items():
+        a = {**good, **change}
+        before = [a[k].clone() for k in ("kc", "vc")]
+        for name, call in calls.items():
+            with pytest.raises(RuntimeError):
+                call(a)
+                pytest.fail(f"{name} accepted {what}")
+        for k, b in zip(("kc", "vc"), before):
+            assert torch.equal(bits(a[k].contiguous()), bits(b.contiguous())), f"{what}: a refused call wrote to {k}"
+
+
 # --------------------------------------------------------------------------- partials
 def check_partials(case, ops, dev):
     """The (m, l, o) partial of the target's split: m = target score * log2 e, l = 1, o = V[target],
