@@ -117,6 +117,24 @@ __device__ __forceinline__ int xcd_balance(int orig, int nwg, int BH, int G) {
   return outer * BH + bh;
 }
 
+// ---- sampler noise (decode.hip sample_kernel, sampling.hip sample_topkp_kernel) ----
+// Gumbel noise -log(-log u) of token `idx` at (seed, step): a 32-bit integer hash, its top 24
+// bits as u = (h >> 8 + 0.5) * 2^-24.  Above 2^23 the f32 sum rounds to even, so
+// h >> 8 == 0xFFFFFF would give u == 1.0f, -log u == -0.0 and a score of +inf: that token won
+// whatever its logit (2^-24 per token and draw).  u is clamped to the largest f32 below 1;
+// every other value is unchanged.  One function for both kernels: a request's draws do not
+// depend on which of them serves it.
+__device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
+  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+  return h;
+}
+__device__ __forceinline__ float gumbel_noise(uint32_t seed, uint32_t step, uint32_t idx) {
+  const uint32_t h = hash3(seed, step, idx);
+  const float u = fminf(((h >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+  return -__logf(-__logf(u));
+}
+
 // ---- KV cache addressing (decode kernels) ----
 // Per layer the cache is [rows, Hkv, SEQ, D] bf16.  Contiguous (bt == nullptr): rows =
 // slots, SEQ = max_seq.  Paged (bt = block table [slots, maxb] int32): rows = pool blocks,

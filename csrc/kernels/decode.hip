@@ -749,12 +749,6 @@ __global__ void __launch_bounds__(256, 2) decode_attn_kv8_kernel(
   decode_split_body(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, 0);
 }
 
-__device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-  return h;
-}
-
 // logits [B, V] (bf16 or f32); temperature <= 0 -> greedy.  out ids [B] int64.
 //
 // Split over the vocabulary: grid (nchunks, B), each workgroup reduces `chunk`
@@ -809,11 +803,7 @@ __global__ void __launch_bounds__(256) sample_kernel(const T* __restrict__ logit
       const int c = cb + 256 * u;
       if (c >= c1) break;
       float w = v[u];
-      if (inv_temp > 0.f) {
-        const uint32_t h = hash3(nseed, step, (uint32_t)c);
-        const float uu = ((h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        w = w * inv_temp - __logf(-__logf(uu));  // Gumbel-max
-      }
+      if (inv_temp > 0.f) w = w * inv_temp + gumbel_noise(nseed, step, (uint32_t)c);  // Gumbel-max
       if (w > best) { best = w; bi = c; }
     }
   }

@@ -9,7 +9,8 @@
 //
 // (Rows without top-k / top-p take decode.hip's vocabulary-split kernel instead, same draws;
 // mxllm/ops/decode.py sample_rows routes them.)  Here: one 1024-thread workgroup per row, no sort:
-//  * logits map to order-preserving 32-bit keys (bf16 -> its exact f32);
+//  * logits map to order-preserving 32-bit keys (bf16 -> its exact f32; -0.0 and
+//    +0.0 share one key, so a boundary at zero keeps both);
 //  * the k-th largest key and then the top-p boundary key are found by a
 //    radix select, 11 + 11 + 10 bits, over LDS histograms: counts for top-k,
 //    softmax masses exp2((x - max) * log2e / T) for top-p (restricted to the
@@ -17,8 +18,9 @@
 //  * the draw is Gumbel-max restricted to keys >= the boundary: argmax of
 //    x / T + G(seed, step, index) is an EXACT sample of the renormalised
 //    distribution over that set, with the same (seed, step, index) noise as the
-//    greedy/temperature kernel in decode.hip, so a request's stream does not
-//    depend on batching;
+//    greedy/temperature kernel in decode.hip (common.h gumbel_noise: u strictly
+//    inside (0, 1), so no token's score is infinite), so a request's stream does
+//    not depend on batching;
 //  * every pass streams the row (256 KB bf16 at a 128k vocabulary) from L2 with
 //    16-B loads.
 // The LDS mass histogram uses float atomics: a boundary whose cumulative mass
@@ -28,18 +30,15 @@
 
 namespace mx {
 
+// order-preserving key of a logit; -0.0 takes the key of +0.0 (they compare equal, so a
+// boundary on either keeps both)
 __device__ __forceinline__ uint32_t okey(float f) {
-  const uint32_t b = __float_as_uint(f);
+  uint32_t b = __float_as_uint(f);
+  if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float key2f(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ uint32_t hash3s(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-  return h;
 }
 
 constexpr int kSampThreads = 1024;
@@ -220,9 +219,7 @@ __global__ void __launch_bounds__(kSampThreads) sample_topkp_kernel(
   int gi = 0x7fffffff;
   rd.each([&](int idx, float v) {
     if (okey(v) < tf) return;
-    const uint32_t h = hash3s(seed, step, (uint32_t)idx);  // = decode.hip sample_kernel noise of a 1-row call
-    const float u = ((h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float s = v * inv_t - __logf(-__logf(u));
+    const float s = v * inv_t + gumbel_noise(seed, step, (uint32_t)idx);  // the noise of decode.hip's sample_kernel
     if (s > gb || (s == gb && idx < gi)) { gb = s; gi = idx; }
   });
   argmax_reduce(gb, gi);
