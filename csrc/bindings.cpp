@@ -1430,6 +1430,77 @@ void lora_grads(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& g, 
   MX_OK(mx_lora_xtg(desc.data(), np, (int)T, 1.0f, accumulate ? 1 : 0, ws.data_ptr<float>(), cur_stream()));
 }
 
+// ---------------------------------------------------------------- multi-adapter LoRA for serving (lora_serve.hip)
+// The operand check of lora_gather_shrink and lora_gather_expand_add_ (op: the caller's name): the
+// rows (x or y), the per-row adapter ids, the table those rows gather from and the partials
+// between the two launches.  Every check runs before anything is launched or written.
+struct LoraServeCall {
+  int64_t M, W, ld, n_adapters, KS, R;  // W: the rows' width (K of x, N of y)
+  const int32_t* ids;
+};
+static LoraServeCall check_lora_serve(const char* op, const at::Tensor& rows, const char* rows_name,
+                                      const at::Tensor& ids, const at::Tensor& tab, int64_t tab_w_dim,
+                                      const at::Tensor& partials, int64_t K) {
+  MX_CHECK(rows.is_cuda() && rows.scalar_type() == at::kBFloat16 && rows.dim() == 2 && rows.size(0) >= 1, op, ": ",
+           rows_name, " must be a bfloat16 [M, ", tab_w_dim == 2 ? "K" : "N", "] GPU tensor with M >= 1");
+  MX_CHECK(rows.stride(1) == 1 && rows.stride(0) >= rows.size(1) && rows.stride(0) % 8 == 0 &&
+               reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
+           op, ": ", rows_name, " must be a 16-byte aligned row-major view with a row stride that is a multiple of 8");
+  LoraServeCall c{rows.size(0), rows.size(1), rows.stride(0), 0, 0, 0, nullptr};
+  MX_CHECK(c.W >= 8 && c.W % 8 == 0, op, ": ", rows_name, " has ", c.W, " columns, not a positive multiple of 8");
+  MX_CHECK(c.M < (int64_t(1) << 31) && c.ld < (int64_t(1) << 31), op, ": ", rows_name, " is too large");
+  c.ids = check_rows_i32(ids, rows.device(), c.M, op, "ids");
+  MX_CHECK(c.ids != nullptr, op, ": ids");
+  MX_CHECK(tab.device() == rows.device() && tab.scalar_type() == at::kBFloat16 && tab.is_contiguous() &&
+               tab.dim() == 3 && tab.size(0) >= 1 && tab.size(tab_w_dim) == c.W,
+           op, ": the table must be a contiguous bfloat16 ", tab_w_dim == 2 ? "[n_adapters, R, K]" : "[n_adapters, N, r_max]",
+           " tensor on ", rows_name, "'s device whose ", tab_w_dim == 2 ? "K" : "N", " is ", c.W);
+  c.n_adapters = tab.size(0);
+  c.KS = mx_lora_serve_ksplits((int)(tab_w_dim == 2 ? c.W : K));
+  MX_CHECK(partials.device() == rows.device() && partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
+               partials.dim() == 3 && partials.size(0) == c.KS && partials.size(1) == c.M,
+           op, ": partials must be a contiguous float32 [", c.KS, ", ", c.M, ", R] tensor on ", rows_name, "'s device");
+  c.R = partials.size(2);
+  return c;
+}
+
+// x [M, K] -> partials [ceil(K / 512), M, R] (written for the rows whose id is >= 0)
+void lora_gather_shrink(const at::Tensor& x, const at::Tensor& ids, const at::Tensor& a_tab, at::Tensor partials) {
+  const LoraServeCall c = check_lora_serve("lora_gather_shrink", x, "x", ids, a_tab, 2, partials, 0);
+  MX_CHECK(a_tab.size(1) == c.R && c.R % 8 == 0 && c.R >= 8 && c.R <= 192, "lora_gather_shrink: A_tab holds ",
+           a_tab.size(1), " rows per adapter and partials ", c.R, "; both must be n_splits * r_max <= 192");
+  DevGuard g(x.device());
+  MX_OK(mx_lora_gather_shrink(bf(x), c.ld, c.ids, bf(a_tab), partials.data_ptr<float>(), (int)c.M, (int)c.W, (int)c.R,
+                              (int)c.n_adapters, cur_stream()));
+}
+
+// y [M, N] += s * t B^T per row, t = the sum of the partials over the K splits of a projection of K inputs
+void lora_gather_expand_add_(at::Tensor y, const at::Tensor& partials, const at::Tensor& ids, const at::Tensor& b_tab,
+                             const at::Tensor& s_tab, at::IntArrayRef splits, int64_t K) {
+  const char* op = "lora_gather_expand_add_";
+  MX_CHECK(K >= 8 && K % 8 == 0 && K < (int64_t(1) << 31), op, ": K must be a positive multiple of 8");
+  const LoraServeCall c = check_lora_serve(op, y, "y", ids, b_tab, 1, partials, K);
+  const int64_t r_max = b_tab.size(2), ns = (int64_t)splits.size();
+  MX_CHECK(r_max == 8 || r_max == 16 || r_max == 32 || r_max == 64, op, ": r_max must be 8, 16, 32 or 64, got ", r_max);
+  MX_CHECK(ns >= 1 && ns <= 3, op, ": 1 to 3 splits, got ", ns);
+  int sp[3] = {0, 0, 0};
+  int64_t sum = 0;
+  for (int64_t i = 0; i < ns; ++i) {
+    MX_CHECK(splits[i] >= 8 && splits[i] % 8 == 0, op, ": every split must be a positive multiple of 8, got ", splits[i]);
+    sp[i] = (int)splits[i];
+    sum += splits[i];
+  }
+  MX_CHECK(sum == c.W, op, ": the splits sum to ", sum, ", y has ", c.W, " columns");
+  MX_CHECK(c.R == ns * r_max, op, ": partials hold ", c.R, " columns, expected n_splits * r_max = ", ns * r_max);
+  MX_CHECK(s_tab.device() == y.device() && s_tab.scalar_type() == at::kFloat && s_tab.is_contiguous() &&
+               s_tab.dim() == 1 && s_tab.size(0) == c.n_adapters,
+           op, ": s_tab must be a contiguous float32 [n_adapters] tensor on y's device");
+  DevGuard g(y.device());
+  MX_OK(mx_lora_gather_expand_add(bfm(y), c.ld, partials.data_ptr<float>(), c.ids, bf(b_tab), s_tab.data_ptr<float>(),
+                                  (int)c.M, (int)c.W, (int)c.KS, (int)r_max, sp, (int)ns, (int)c.n_adapters,
+                                  cur_stream()));
+}
+
 TORCH_LIBRARY(mxllm, m) {
   m.def("rmsnorm_fwd(Tensor x, Tensor? res, Tensor w, float eps, int out_pad=0) -> (Tensor, Tensor, Tensor)");
   m.def("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres, bool need_dw, int out_pad=0) -> (Tensor, Tensor)");
@@ -1487,6 +1558,8 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("lora_xwt(Tensor x, Tensor v, Tensor(a!) out, float alpha, int rows=0) -> ()");
   m.def("swiglu_lora(Tensor? dm, Tensor gu, int pad, Tensor v, int nrb, float alpha) -> Tensor");
   m.def("lora_grads(Tensor x, Tensor dy, Tensor g, Tensor st, Tensor(a!) ga, Tensor(b!) gb, int[] splits, int r, bool accumulate) -> ()");
+  m.def("lora_gather_shrink(Tensor x, Tensor ids, Tensor a_tab, Tensor(a!) partials) -> ()");
+  m.def("lora_gather_expand_add_(Tensor(a!) y, Tensor partials, Tensor ids, Tensor b_tab, Tensor s_tab, int[] splits, int K) -> ()");
   m.def("attn_bwd_ablate(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, int mode, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, int dq_mode=3, Tensor? dq_out=None, Tensor? dk_out=None, Tensor? dv_out=None) -> (Tensor, Tensor, Tensor)");
   m.def("attn_bwd_rope(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor cos, Tensor sin, int out_pad=0) -> Tensor");
@@ -1549,4 +1622,6 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("lora_xwt", &lora_xwt);
   m.impl("swiglu_lora", &swiglu_lora);
   m.impl("lora_grads", &lora_grads);
+  m.impl("lora_gather_shrink", &lora_gather_shrink);
+  m.impl("lora_gather_expand_add_", &lora_gather_expand_add_);
 }

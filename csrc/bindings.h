@@ -110,6 +110,14 @@ int mx_lora_xwt(const uint16_t* X, int64_t ldx, const uint16_t* V, int64_t ldv, 
                 float* ws, int M, int K, float alpha, int rows, hipStream_t stream);
 int mx_lora_xtg(const int64_t* desc, int np, int T, float alpha, int accumulate, float* ws, hipStream_t stream);
 
+// lora_serve.hip
+int mx_lora_serve_ksplits(int K);
+int mx_lora_gather_shrink(const uint16_t* x, int64_t ldx, const int32_t* ids, const uint16_t* a_tab, float* part,
+                          int M, int K, int R, int n_adapters, hipStream_t stream);
+int mx_lora_gather_expand_add(uint16_t* y, int64_t ldy, const float* part, const int32_t* ids, const uint16_t* b_tab,
+                              const float* s_tab, int M, int N, int KS, int r_max, const int* splits, int n_splits,
+                              int n_adapters, hipStream_t stream);
+
 // misc.hip
 int mx_copy2d_batched(const int64_t* desc, int n, int64_t total_blocks, hipStream_t stream);
 int mx_segmented_mean_i32(const int32_t* codes, const int64_t* offs, float* out, int nseg,

@@ -75,6 +75,7 @@ class RunConfig:
     ckpt_dir: str = ""
     save_every: int = 0
     save_hf: str = ""  # at the end: write the model as a Hugging Face Llama directory (LoRA merged)
+    save_adapter: str = ""  # at the end: write the LoRA adapter alone as a PEFT directory (mxllm/models/adapter.py)
     resume: bool = True
     log_every: int = 10
     metrics_file: str = ""

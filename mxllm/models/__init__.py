@@ -1,6 +1,7 @@
 from .config import LlamaConfig, PRESETS, get_config  # noqa: F401
 from .llama import Llama, FusedLinear  # noqa: F401
 from .hf import is_hf_dir, load_hf_config, load_hf_llama, save_hf_llama  # noqa: F401
+from .adapter import load_adapter, save_adapter  # noqa: F401
 
 
 def model_config(name: str) -> LlamaConfig:

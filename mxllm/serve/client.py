@@ -117,6 +117,18 @@ def _local_engine(model: str):
     raise CompletionError(f"no local engine registered for model {model!r}")
 
 
+def _local_route(model: str):
+    """(engine, tokenizer, adapter) for ``model``: a registered name is that engine's base model;
+    the name of a LoRA adapter loaded into a registered engine reaches that engine with the
+    adapter; otherwise ``_local_engine``'s rule, on the base model."""
+    if model not in _LOCAL:
+        for eng, tok in _LOCAL.values():
+            if model in getattr(eng, "adapters", {}):
+                return eng, tok, model
+    eng, tok = _local_engine(model)
+    return eng, tok, None
+
+
 # request fields forwarded to an HTTP endpoint besides model / messages / max_tokens / temperature
 _FORWARD = ("top_p", "stop", "seed", "top_k", "presence_penalty", "frequency_penalty", "repetition_penalty",
             "logit_bias", "logprobs", "top_logprobs")
@@ -160,11 +172,12 @@ def _text_logprobs(tok, toks, entries) -> dict:
 
 
 def _local(model, messages, max_tokens, temperature, **kw) -> ModelResponse:
-    eng, tok = _local_engine(model)
+    eng, tok, adapter = _local_route(model)
     ids = tok.apply_chat_template(messages)
     ekw = _engine_kw(kw, chat=True)
     r = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature,
-                     top_p=kw.get("top_p", 1.0), seed=kw.get("seed", 0), return_requests=True, **ekw)[0]
+                     top_p=kw.get("top_p", 1.0), seed=kw.get("seed", 0), return_requests=True,
+                     adapters=[adapter] if adapter else None, **ekw)[0]
     if r.error:
         raise CompletionError(f"local engine: {r.error}")
     out = r.output
@@ -241,13 +254,13 @@ def _local_stream(model, messages, max_tokens, temperature, **kw):
     """Token deltas from the in-process engine's background loop as they are produced."""
     from .engine import SamplingParams
 
-    eng, tok = _local_engine(model)
+    eng, tok, adapter = _local_route(model)
     eng.start()
     ids = tok.apply_chat_template(messages)
     ekw = _engine_kw(kw, chat=True)
     r = eng.submit(ids, SamplingParams(max_new_tokens=max_tokens, temperature=temperature,
                                        top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0), seed=kw.get("seed", 0),
-                                       **ekw))
+                                       **ekw), adapter)
     sent, first = 0, True
     while True:
         done = r.done.wait(0.002)
@@ -430,11 +443,12 @@ def text_completion(model: str, prompt: str, *, api_base: str | None = None, api
     """LiteLLM ``text_completion``: a raw prompt (no chat template); ``.choices[0].text``."""
     base = api_base if api_base is not None else globals()["api_base"]
     if _is_local(base):
-        eng, tok = _local_engine(model)
+        eng, tok, adapter = _local_route(model)
         ids = tok.encode(prompt)
         ekw = _engine_kw(kw, chat=False)
         r = eng.generate([ids], max_new_tokens=max_tokens, temperature=temperature, top_p=kw.get("top_p", 1.0),
-                         top_k=kw.get("top_k", 0), seed=kw.get("seed", 0), return_requests=True, **ekw)[0]
+                         top_k=kw.get("top_k", 0), seed=kw.get("seed", 0), return_requests=True,
+                         adapters=[adapter] if adapter else None, **ekw)[0]
         if r.error:
             raise CompletionError(f"local engine: {r.error}")
         out = r.output

@@ -26,6 +26,13 @@ entries that write into a scratch cache slot, the split-K decode kernel gets
 a power-of-two key bound (splits past a sequence's length exit at once), and
 the step's only host->device traffic is one [3, B] int64 copy of
 (token, position, slot).
+
+LoRA adapters (``max_adapters`` > 0): one copy of the base weights and static tables of adapters;
+a request names its adapter and requests with different adapters share a batch.  The step input
+is then [4, B] (the fourth row: each row's adapter table slot, -1 = none) and graphs are keyed
+(batch bucket, key bucket, any_adapter): a step in which no row has an adapter replays the same
+fused launches as an engine without tables; a step with adapters runs every projection unfused
+followed by the two gather kernels of ``ops.lora_delta_rows_``.
 """
 from __future__ import annotations
 
@@ -138,6 +145,7 @@ class Request:
     error: str | None = None
     # one (logprob, [(token id, logprob), ...]) per output token when params.logprobs is set
     logprobs: list = field(default_factory=list)
+    adapter: str | None = None  # name of a loaded LoRA adapter (Engine.load_adapter); None = the base model
 
     def __post_init__(self):
         # any penalty / logit_bias / logprobs: the request takes the adjusted sampling path
@@ -147,7 +155,8 @@ class Request:
 class Engine:
     def __init__(self, model, max_batch: int = 8, max_seq: int = 4096, device=None, eos_ids=(),
                  use_graphs: bool | None = None, prefill_tokens: int = 16384, tp_group=None,
-                 kv_pool_tokens: int | None = None, kv_block: int = 256, kv_dtype: str | None = None):
+                 kv_pool_tokens: int | None = None, kv_block: int = 256, kv_dtype: str | None = None,
+                 max_adapters: int = 0, max_lora_rank: int = 16):
         """``tp_group``: serve a tensor-parallel shard (mxllm/parallel/tensor.py
         ``shard_llama`` / ``random_shard``) with the other ranks of the group;
         every rank of the group runs the same schedule (same submissions in the
@@ -159,7 +168,15 @@ class Engine:
         (mxllm/serve/kvcache.py; head_dim 128): prefill attends over the fresh bf16 K/V and only
         the cache write quantises; a decode step runs RMSNorm + QKV GEMM + ``rope_append_kv8`` +
         ``decode_attn_kv8`` (the fused QKV epilogue cannot see a whole row's amax, so
-        MXLLM_ROPE_FUSED, MXLLM_DECODE_COMBINE=fused and MXLLM_MERGE_FUSED do not apply)."""
+        MXLLM_ROPE_FUSED, MXLLM_DECODE_COMBINE=fused and MXLLM_MERGE_FUSED do not apply).
+        ``max_adapters`` > 0: serve that many LoRA adapters beside the base weights
+        (``load_adapter``; a request names its adapter), each of rank <= ``max_lora_rank`` (8, 16,
+        32 or 64).  The tables (mxllm/ops/lora_serve.py ``AdapterTables``) are allocated once; 0
+        allocates nothing and leaves every code path as it is without adapters."""
+        if max_adapters < 0:
+            raise ValueError(f"max_adapters must be >= 0, got {max_adapters}")
+        if max_adapters > 0 and tp_group is not None:
+            raise ValueError("LoRA adapters are served by single-GPU engines (tp_group with max_adapters > 0)")
         self.model = model
         self.tp = None
         if tp_group is not None:
@@ -217,6 +234,13 @@ class Engine:
             self._attn_cnt = torch.zeros((n_slots + 64) * self.kv.k[0].shape[1], dtype=torch.int32,
                                          device=self.device)
         self._pf_stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" and _PREFETCH else None
+        # LoRA adapters: static tables, name -> table slot, and the adapter (table slot, -1 = none)
+        # of the sequence in each cache slot
+        self.lora = None
+        self.adapters: dict[str, int] = {}
+        self.slot_adapter = [-1] * n_slots
+        if max_adapters > 0:
+            self.lora = ops.AdapterTables(c, max_adapters, max_lora_rank, self.device, max_rows=max_batch, dtype=dt)
         self.eos_ids = tuple(eos_ids) if eos_ids else (c.eos_id,)
         self.free_slots = list(range(max_batch))
         self.active: dict[int, Request] = {}
@@ -270,9 +294,12 @@ class Engine:
         return mid, h
 
     @torch.no_grad()
-    def _layers(self, x: torch.Tensor, attn_fn, qkv_fn=None) -> torch.Tensor:
+    def _layers(self, x: torch.Tensor, attn_fn, qkv_fn=None, lora=None) -> torch.Tensor:
         """``qkv_fn(i, delta, h, gamma, layer)`` (decode): the fused norm + QKV + RoPE/cache-append
-        projection returning (rotated q, new residual) or None; ``attn_fn(i, qkv, q=None)``."""
+        projection returning (rotated q, new residual) or None; ``attn_fn(i, qkv, q=None)``.
+        ``lora(i, proj, y, x)``: the pass has rows on LoRA adapters (``_layers_lora``)."""
+        if lora is not None:
+            return self._layers_lora(x, attn_fn, lora)
         m, c = self.model, self.cfg
         h = x
         delta, gamma = None, m.layers[0].attn_norm  # sub-block output not yet added to h, next norm
@@ -299,6 +326,34 @@ class Engine:
             return ops.rms_norm(h, gamma, c.norm_eps)
         xn, h = ops.add_rms_norm(delta, h, gamma, c.norm_eps)
         return xn
+
+    def _layers_lora(self, x: torch.Tensor, attn_fn, lora) -> torch.Tensor:
+        """``_layers`` for a pass with rows on LoRA adapters: ``lora(i, proj, y, x)`` adds the rows'
+        deltas to the projection output y in place.  The unfused route -- RMSNorm kernel, projection,
+        delta, ``attn_fn(i, qkv)``, SwiGLU kernel; no GEMM prologue or epilogue -- whatever the
+        projection's class (``FusedLinear``, ``W8Linear``)."""
+        m, c = self.model, self.cfg
+        h, delta, gamma = x, None, m.layers[0].attn_norm
+        for i, layer in enumerate(m.layers):
+            if delta is None:
+                xn = ops.rms_norm(h, gamma, c.norm_eps)
+            else:
+                xn, h = ops.add_rms_norm(delta, h, gamma, c.norm_eps)
+            qkv = layer.wqkv(xn)
+            lora(i, "wqkv", qkv, xn)
+            o = attn_fn(i, qkv)
+            a = layer.wo(o)
+            lora(i, "wo", a, o)
+            xn, h = ops.add_rms_norm(a, h, layer.mlp_norm, c.norm_eps)
+            gu = layer.wgu(xn)
+            lora(i, "wgu", gu, xn)
+            mid = ops.swiglu(gu)
+            d = layer.wd(mid)
+            lora(i, "wd", d, mid)
+            delta, gamma = d, (m.layers[i + 1].attn_norm if i + 1 < len(m.layers) else m.final_norm)
+        if delta is None:
+            return ops.rms_norm(h, gamma, c.norm_eps)
+        return ops.add_rms_norm(delta, h, gamma, c.norm_eps)[0]
 
     @property
     def k_cache(self):
@@ -339,7 +394,16 @@ class Engine:
 
         xn = self._layers(x, attn)
         self.lens[slot] = S
+        self.slot_adapter[slot] = -1
         return self._logits(xn[-1:]).float()[0]
+
+    def _adapter_index(self, name) -> int:
+        """Table slot of the adapter ``name`` (None: -1, the base model)."""
+        if name is None:
+            return -1
+        if self.lora is None or name not in self.adapters:
+            raise ValueError(f"unknown LoRA adapter {name!r}")
+        return self.adapters[name]
 
     def _logits(self, xn: torch.Tensor) -> torch.Tensor:
         out = ops.linear(xn, self.model.head_weight)  # decode rows: the weight-streaming HIP GEMM
@@ -348,15 +412,21 @@ class Engine:
         return out
 
     @torch.no_grad()
-    def prefill_batch(self, slots: list[int], prompts: list[list[int]]) -> torch.Tensor:
+    def prefill_batch(self, slots: list[int], prompts: list[list[int]], adapters=None) -> torch.Tensor:
         """Prefill several prompts in ONE pass: their tokens are concatenated so
         every GEMM / norm / SwiGLU runs once over all of them (each weight is
         read once per batch instead of once per prompt); attention runs per
-        sequence into its own cache slot.  Returns last-position logits [n, V] f32."""
+        sequence into its own cache slot.  Returns last-position logits [n, V] f32.
+        ``adapters``: one loaded adapter's name or None per prompt; the sequences keep their
+        adapter in the decode steps that follow.  Each of the four projections then adds the
+        delta of the runs of tokens that share an adapter (``lora_delta_rows_`` segments)."""
         m, c = self.model, self.cfg
         lens = [len(p) for p in prompts]
         if any(S >= self.max_seq for S in lens):
             raise ValueError(f"prompt exceeds max_seq {self.max_seq}")
+        aidx = [self._adapter_index(a) for a in adapters] if adapters is not None else [-1] * len(prompts)
+        if len(aidx) != len(prompts):
+            raise ValueError("one adapter (or None) per prompt")
         for s_, S in zip(slots, lens):
             self._ensure(s_, S + 1)
         t = torch.tensor([tok for p in prompts for tok in p], dtype=torch.long, device=self.device)
@@ -372,9 +442,17 @@ class Engine:
                     for j in range(len(prompts))]
             return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
-        xn = self._layers(x, attn)
-        for s_, S in zip(slots, lens):
+        lora = None
+        if any(a >= 0 for a in aidx):
+            segs = ops.lora_serve.merge_segments([a for a, S in zip(aidx, lens) for _ in range(S)])
+
+            def lora(i, proj, y, xin):
+                ops.lora_delta_rows_(y, xin, None, self.lora.layers[i][proj], segments=segs)
+
+        xn = self._layers(x, attn, lora=lora)
+        for s_, S, a in zip(slots, lens, aidx):
             self.lens[s_] = S
+            self.slot_adapter[s_] = a
         last = torch.tensor([o - 1 for o in offs[1:]], device=self.device)
         return self._logits(xn.index_select(0, last)).float()
 
@@ -385,23 +463,37 @@ class Engine:
         max_len = max(self.lens[s] for s in slots) + 1
         for s in slots:
             self._ensure(s, self.lens[s] + 1)
+        # each row's adapter (table slot, -1 = none); a step in which no row has one is today's step
+        aidx = [self.slot_adapter[s] for s in slots] if self.lora is not None else None
+        any_adapter = aidx is not None and any(a >= 0 for a in aidx)
         if self.use_graphs:
-            logits = self._decode_graphed(slots, tokens, max_len)
+            logits = self._decode_graphed(slots, tokens, max_len, aidx, any_adapter)
         else:
-            inp = torch.stack([tokens.to(self.device, torch.long),
-                               torch.tensor([self.lens[s] for s in slots], device=self.device),
-                               torch.tensor(slots, device=self.device)])
-            logits = self._decode_body(inp, max_len)
+            rows = [tokens.to(self.device, torch.long),
+                    torch.tensor([self.lens[s] for s in slots], device=self.device),
+                    torch.tensor(slots, device=self.device)]
+            if aidx is not None:
+                rows.append(torch.tensor(aidx, device=self.device))
+            logits = self._decode_body(torch.stack(rows), max_len, any_adapter)
         for s in slots:
             self.lens[s] += 1
         return logits[:B]
 
-    def _decode_body(self, inp: torch.Tensor, max_len: int) -> torch.Tensor:
-        """inp int64 [3, B] = (token, position of the new token, cache slot)."""
+    def _decode_body(self, inp: torch.Tensor, max_len: int, any_adapter: bool = False) -> torch.Tensor:
+        """inp int64 [3, B] = (token, position of the new token, cache slot); an engine with adapter
+        tables: [4, B], the fourth row each row's adapter table slot (-1 = none).  ``any_adapter``:
+        some row has one -- the step runs unfused and every projection adds the rows' deltas
+        (``lora_delta_rows_``); otherwise the fourth row is not looked at."""
         m, c = self.model, self.cfg
         pos = inp[1].to(torch.int32)
         sl = inp[2].to(torch.int32)
         x = ops.embedding(inp[0], m.tok_emb)
+        lora = None
+        if any_adapter:
+            ids = inp[3].to(torch.int32)
+
+            def lora(i, proj, y, xin):
+                ops.lora_delta_rows_(y, xin, ids, self.lora.layers[i][proj])
 
         bt = self.kv.bt
         B = inp.shape[1]
@@ -468,7 +560,7 @@ class Engine:
             q, _ = ops.qkv_rope_linear(None, xn, None, c.norm_eps, *rope)
             return q, h
 
-        xn = self._layers(x, attn, qkv_fn)
+        xn = self._layers(x, attn, qkv_fn if lora is None else None, lora=lora)
         return self._logits(xn)
 
     def _buckets(self, B: int, max_len: int) -> tuple[int, int]:
@@ -482,13 +574,17 @@ class Engine:
             nb *= 2
         return bb, min(nb, cap) * 256
 
-    def _decode_graphed(self, slots: list[int], tokens: torch.Tensor, max_len: int) -> torch.Tensor:
+    def _decode_graphed(self, slots: list[int], tokens: torch.Tensor, max_len: int, aidx=None,
+                        any_adapter: bool = False) -> torch.Tensor:
         B = len(slots)
         bb, kl = self._buckets(B, max_len)
-        entry = self._graphs.get((bb, kl))
+        entry = self._graphs.get((bb, kl, any_adapter))
         if entry is None:
-            entry = self._capture(bb, kl)
+            entry = self._capture(bb, kl, any_adapter)
         inp, out, graph, host = entry
+        if aidx is not None:  # padding rows: no adapter
+            host[3, :B] = torch.tensor(aidx)
+            host[3, B:] = -1
         # the previous step's copy from ``host`` has completed: its logits were
         # read back (sampling) before this step was scheduled
         host[0, :B] = tokens.to("cpu", torch.long)
@@ -501,24 +597,27 @@ class Engine:
         graph.replay()
         return out
 
-    def _capture(self, bb: int, kl: int):
-        inp = torch.zeros(3, bb, dtype=torch.long, device=self.device)
+    def _capture(self, bb: int, kl: int, any_adapter: bool = False):
+        """One graph per (batch bucket, key bucket, any_adapter).  The adapter tables are static
+        buffers read through the step's ids, so loading or unloading an adapter leaves every
+        captured graph valid; warm-up rows use table slot 0, whatever it holds."""
+        inp = torch.zeros(3 if self.lora is None else 4, bb, dtype=torch.long, device=self.device)
         inp[2].fill_(self.scratch_slot)  # warm-up / capture traffic goes to the scratch slot
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(2):  # library handles / workspace set up outside capture
-                self._decode_body(inp, kl)
+                self._decode_body(inp, kl, any_adapter)
         torch.cuda.current_stream(self.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
         with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-            out = self._decode_body(inp, kl)
-        host = torch.empty(3, bb, dtype=torch.long, pin_memory=True)
-        self._graphs[(bb, kl)] = (inp, out, graph, host)
-        log.debug("captured decode graph: batch %d, key bound %d", bb, kl)
-        return self._graphs[(bb, kl)]
+            out = self._decode_body(inp, kl, any_adapter)
+        host = torch.empty(inp.shape[0], bb, dtype=torch.long, pin_memory=True)
+        self._graphs[(bb, kl, any_adapter)] = (inp, out, graph, host)
+        log.debug("captured decode graph: batch %d, key bound %d, adapters %s", bb, kl, any_adapter)
+        return self._graphs[(bb, kl, any_adapter)]
 
     # ------------------------------------------------------------------ scheduling
     # ------------------------------------------------------------------ embeddings
@@ -537,11 +636,13 @@ class Engine:
             out.append(torch.nn.functional.normalize(h.mean(0), dim=0))
         return torch.stack(out).cpu()
 
-    def embed(self, prompts: list[list[int]]) -> torch.Tensor:
+    def embed(self, prompts: list[list[int]], adapter: str | None = None) -> torch.Tensor:
         """Sentence embeddings [n, hidden] (f32, unit norm): the mean of the final
         normed hidden states over each input's tokens.  With the background loop
         running the pass runs on the engine thread between decode steps (it shares
         the model's kernels and workspaces with generation); otherwise inline."""
+        if adapter is not None:
+            raise NotImplementedError("embeddings with a LoRA adapter are not supported")
         if self._thread is None:
             return self._embed_now(prompts)
         box, ev = {}, threading.Event()
@@ -567,8 +668,71 @@ class Engine:
         for t in tasks:
             t()
 
-    def submit(self, prompt: list[int], params: SamplingParams | None = None) -> Request:
-        r = Request(next(self._ids), list(prompt), params or SamplingParams())
+    # ------------------------------------------------------------------ LoRA adapters
+    def _between_steps(self, fn):
+        """Run ``fn`` on the engine thread between steps when the loop is running, else inline."""
+        if self._thread is None or threading.current_thread() is self._thread:
+            return fn()
+        box, ev = {}, threading.Event()
+
+        def task():
+            try:
+                box["out"] = fn()
+            except Exception as e:  # noqa: BLE001
+                box["err"] = e
+            ev.set()
+
+        with self._cv:
+            self._tasks.append(task)
+            self._cv.notify()
+        ev.wait()
+        if "err" in box:
+            raise box["err"]
+        return box["out"]
+
+    def load_adapter(self, name: str, path_or_tensors) -> int:
+        """Load a LoRA adapter (a PEFT directory, or what ``mxllm.models.adapter.load_adapter``
+        returns) into a free table slot under ``name``; requests then name it.  The copy runs
+        between steps; the tables are static, so no captured graph is invalidated.  Returns the slot."""
+        if self.lora is None:
+            raise ValueError("this engine has no adapter tables (max_adapters = 0)")
+        if not isinstance(name, str) or not name:
+            raise ValueError("an adapter needs a non-empty name")
+        ad = path_or_tensors
+        if isinstance(ad, (str, os.PathLike)):
+            from ..models.adapter import load_adapter
+
+            ad = load_adapter(os.fspath(ad), self.cfg, r_max=self.lora.r_max, dtype=self.model.tok_emb.dtype)
+
+        def do():
+            if name in self.adapters:
+                raise ValueError(f"adapter {name!r} is already loaded")
+            used = set(self.adapters.values())
+            free = [i for i in range(self.lora.n_adapters) if i not in used]
+            if not free:
+                raise ValueError(f"all {self.lora.n_adapters} adapter slots are in use")
+            self.lora.put(free[0], ad)
+            self.adapters[name] = free[0]
+            return free[0]
+
+        return self._between_steps(do)
+
+    def unload_adapter(self, name: str) -> None:
+        """Free the adapter's slot (zeroed).  Refused while a waiting or active request uses it."""
+
+        def do():
+            if name not in self.adapters:
+                raise ValueError(f"unknown LoRA adapter {name!r}")
+            with self._lock:
+                busy = any(r.adapter == name for r in list(self.waiting) + list(self.active.values()))
+            if busy:
+                raise ValueError(f"adapter {name!r} is in use by a waiting or active request")
+            self.lora.clear(self.adapters.pop(name))
+
+        return self._between_steps(do)
+
+    def submit(self, prompt: list[int], params: SamplingParams | None = None, adapter: str | None = None) -> Request:
+        r = Request(next(self._ids), list(prompt), params or SamplingParams(), adapter=adapter)
         with self._cv:
             self.waiting.append(r)
             self._cv.notify()
@@ -582,7 +746,8 @@ class Engine:
                 "mean_ttft_s": self.ttft_sum / n, "mean_latency_s": self.latency_sum / n,
                 "prefill_tokens_per_s": self.prefill_tokens / self.prefill_s if self.prefill_s else 0.0,
                 "decode_tokens_per_s": self.decode_tokens / self.decode_s if self.decode_s else 0.0,
-                "decode_steps": self.steps, "kv_cache_dtype": self.kv_dtype, "kv_cache_bytes": self.kv.nbytes()}
+                "decode_steps": self.steps, "kv_cache_dtype": self.kv_dtype, "kv_cache_bytes": self.kv.nbytes(),
+                "lora_adapters": sorted(self.adapters)}
 
     def _finish(self, r: Request, reason: str):
         r.finish_reason = reason
@@ -593,6 +758,7 @@ class Engine:
             self.ttft_sum += r.t_first - r.t_submit
         if r.slot >= 0:
             self.kv.release(r.slot)
+            self.slot_adapter[r.slot] = -1
             self.free_slots.append(r.slot)
             self.active.pop(r.slot, None)
             r.slot = -1
@@ -674,6 +840,11 @@ class Engine:
                     r.error = f"logit_bias token id {bad[0]} outside the vocabulary [0, {self.vocab})"
                     rejected.append(r)
                     continue
+                if r.adapter is not None and r.adapter not in self.adapters:
+                    self.waiting.pop(0)
+                    r.error = f"unknown LoRA adapter {r.adapter!r}"
+                    rejected.append(r)
+                    continue
                 if not self.kv.can_reserve(need):  # paged pool full: wait for finishing requests
                     break
                 self.waiting.pop(0)
@@ -700,7 +871,8 @@ class Engine:
         for grp in groups:
             try:
                 t0 = time.perf_counter()
-                logits = self.prefill_batch([r.slot for r in grp], [r.prompt for r in grp])
+                logits = self.prefill_batch([r.slot for r in grp], [r.prompt for r in grp],
+                                            [r.adapter for r in grp] if self.lora is not None else None)
                 for r in grp:
                     self.active[r.slot] = r
                 toks = self._sample(logits, grp, first=True)
@@ -831,12 +1003,14 @@ class Engine:
             out.append(entries)
         return out
 
-    def score(self, prompts: list[list[int]], top: int = 0) -> list[list]:
+    def score(self, prompts: list[list[int]], top: int = 0, adapter: str | None = None) -> list[list]:
         """Prompt scoring: for each prompt one entry per position -- None for the first
         token, then (logprob of token t+1 given tokens <= t, [(id, logprob), ...] of the
         ``top`` most likely tokens there).  One full forward per prompt (no KV cache
         touched), the head GEMM and ``logprob_rows`` over chunks of at most ``SCORE_ROWS``
         rows.  Runs on the engine thread between decode steps like ``embed``."""
+        if adapter is not None:
+            raise NotImplementedError("prompt scoring with a LoRA adapter is not supported")
         if self._thread is None:
             return self._score_now(prompts, top)
         box, ev = {}, threading.Event()
@@ -859,14 +1033,18 @@ class Engine:
     def generate(self, prompts: list[list[int]], max_new_tokens: int = 32, temperature: float = 0.0,
                  top_p: float = 1.0, top_k: int = 0, stop_ids=(), seed: int = 0, *, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, repetition_penalty: float = 1.0, logit_bias: dict | None = None,
-                 logprobs: int | None = None, return_requests: bool = False):
+                 logprobs: int | None = None, return_requests: bool = False, adapters=None):
         """Synchronous batched generation (continuous batching when
         len(prompts) > max_batch).  ``return_requests``: the finished ``Request`` objects
-        (``.output``, ``.logprobs``, ``.finish_reason``, ``.error``) instead of the token lists."""
+        (``.output``, ``.logprobs``, ``.finish_reason``, ``.error``) instead of the token lists.
+        ``adapters``: one loaded LoRA adapter's name or None per prompt."""
+        if adapters is not None and len(adapters) != len(prompts):
+            raise ValueError("adapters: one name or None per prompt")
         reqs = [self.submit(p, SamplingParams(max_new_tokens, temperature, top_p, top_k, tuple(stop_ids), seed,
                                               presence_penalty, frequency_penalty, repetition_penalty,
-                                              dict(logit_bias) if logit_bias else None, logprobs))
-                for p in prompts]
+                                              dict(logit_bias) if logit_bias else None, logprobs),
+                            adapters[i] if adapters is not None else None)
+                for i, p in enumerate(prompts)]
         if self._thread is not None:
             for r in reqs:
                 r.done.wait()

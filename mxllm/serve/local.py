@@ -27,12 +27,14 @@ def preset_for(model_name: str, device: torch.device) -> str:
 
 def ensure_local_engine(model_name: str, device, engine_model: str = "", max_batch: int = 8, max_seq: int = 16384,
                         tokenizer_path: str = "", checkpoint: str = "", seed: int = 0, weights: str = "bf16",
-                        kv_pool_tokens: int = 0, kv_cache: str | None = None):
+                        kv_pool_tokens: int = 0, kv_cache: str | None = None, adapters: dict | None = None,
+                        max_lora_rank: int = 16):
     """Build (once per model name) and register the local engine.  The KV cache is a paged
     pool of ``kv_pool_tokens`` (0: max(max_batch x 4096, max_seq)) shared by every slot, so a
     long context window costs HBM only when a long prompt is admitted; prompts are cut to
     ``max_seq - 64`` tokens (left-truncation) only beyond the window.  ``kv_cache``: "bf16" /
-    "fp8" KV cache (None: env MXLLM_KV_CACHE, default bf16)."""
+    "fp8" KV cache (None: env MXLLM_KV_CACHE, default bf16).  ``adapters``: {name: PEFT LoRA
+    directory} loaded beside the base model; ``completion(model=<name>)`` then runs on that adapter."""
     from ..data.tokenizer import get_tokenizer
     from ..models import build_model, tokenizer_path_for
 
@@ -58,7 +60,9 @@ def ensure_local_engine(model_name: str, device, engine_model: str = "", max_bat
     max_seq = min(max_seq, cfg.max_seq_len)
     pool = kv_pool_tokens or max(max_batch * 4096, max_seq)
     eng = Engine(model, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id,), kv_pool_tokens=pool,
-                 kv_dtype=kv_cache)
+                 kv_dtype=kv_cache, max_adapters=len(adapters or {}), max_lora_rank=max_lora_rank)
+    for name, path in (adapters or {}).items():
+        eng.load_adapter(name, path)
     client.register_local(model_name, eng, _Truncating(tok, max_seq - 64))
     return client._LOCAL[model_name]
 

@@ -90,13 +90,18 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
     def bad_request(e):
         return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
 
-    async def run(prompt_ids, params):
-        r = engine.submit(prompt_ids, params)
+    def adapter_of(body):
+        """The request's ``model`` when it names a loaded LoRA adapter, else None (the base model)."""
+        name = body.get("model")
+        return name if isinstance(name, str) and name in engine.adapters else None
+
+    async def run(prompt_ids, params, adapter=None):
+        r = engine.submit(prompt_ids, params, adapter)
         while not r.done.is_set():
             await asyncio.sleep(0.002)
         if r.error:
             stats["errors"] += 1
-            if "logit_bias" in r.error:  # rejected at admission: the caller's mistake
+            if "logit_bias" in r.error or "LoRA adapter" in r.error:  # rejected at admission: the caller's mistake
                 raise ValueError(r.error)
             raise HTTPException(status_code=500, detail=r.error)
         stats["prompt_tokens"] += len(prompt_ids)
@@ -137,7 +142,9 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
 
     @app.get("/v1/models")
     async def models():
-        return {"object": "list", "data": [{"id": model_name, "object": "model", "owned_by": "mxllm"}]}
+        data = [{"id": model_name, "object": "model", "owned_by": "mxllm"}]
+        data += [{"id": a, "object": "model", "owned_by": "mxllm", "parent": model_name} for a in sorted(engine.adapters)]
+        return {"object": "list", "data": data}
 
     @app.get("/metrics")
     async def metrics():
@@ -154,7 +161,7 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
                  f"mxllm_decode_tokens_total {engine.decode_tokens}",
                  f"mxllm_decode_seconds_total {engine.decode_s:.6f}",
                  f'mxllm_kv_cache_info{{kv_cache_dtype="{engine.kv_dtype}"}} 1',
-                 f"mxllm_kv_cache_bytes {engine.kv.nbytes()}"]
+                 f"mxllm_kv_cache_bytes {engine.kv.nbytes()}", f"mxllm_lora_adapters {len(engine.adapters)}"]
         return PlainTextResponse("\n".join(lines) + "\n")
 
     @app.post("/v1/chat/completions")
@@ -168,8 +175,9 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
         try:
             params = sampling_params(body, chat=True)
             if body.get("stream"):
-                return StreamingResponse(_stream(ids, params, chat=True), media_type="text/event-stream")
-            r = await run(ids, params)
+                return StreamingResponse(_stream(ids, params, chat=True, adapter=adapter_of(body)),
+                                         media_type="text/event-stream")
+            r = await run(ids, params, adapter_of(body))
         except ValueError as e:
             return bad_request(e)
         text = tokenizer.decode([t for t in r.output if t not in engine.eos_ids])
@@ -193,17 +201,18 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
         try:
             params = sampling_params(body, chat=False)
             if body.get("stream"):
-                return StreamingResponse(_stream(ids, params, chat=False), media_type="text/event-stream")
+                return StreamingResponse(_stream(ids, params, chat=False, adapter=adapter_of(body)),
+                                         media_type="text/event-stream")
             scored = None
             if echo and params.logprobs is not None:  # prompt scoring: one full forward, no KV cache
                 scored = (await asyncio.get_running_loop().run_in_executor(
-                    None, engine.score, [ids], params.logprobs))[0]
+                    None, engine.score, [ids], params.logprobs, adapter_of(body)))[0]
             if echo and body.get("max_tokens") == 0:  # nothing generated
                 out, out_lp, reason = [], [], "length"
                 use = {"prompt_tokens": len(ids), "completion_tokens": 0, "total_tokens": len(ids)}
                 stats["prompt_tokens"] += len(ids)
             else:
-                r = await run(ids, params)
+                r = await run(ids, params, adapter_of(body))
                 out, out_lp, reason, use = r.output, r.logprobs, r.finish_reason, usage(r)
         except (ValueError, NotImplementedError) as e:
             return bad_request(e)
@@ -240,7 +249,7 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
             return JSONResponse({"error": {"message": "empty input", "type": "invalid_request_error"}},
                                 status_code=400)
         try:
-            vec = await asyncio.get_running_loop().run_in_executor(None, engine.embed, seqs)
+            vec = await asyncio.get_running_loop().run_in_executor(None, engine.embed, seqs, adapter_of(body))
         except (ValueError, NotImplementedError) as e:
             return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}}, status_code=400)
         n = sum(len(q) for q in seqs)
@@ -249,8 +258,8 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
             "data": [{"object": "embedding", "index": i, "embedding": v.tolist()} for i, v in enumerate(vec)],
             "usage": {"prompt_tokens": n, "total_tokens": n}})
 
-    async def _stream(ids, params, chat: bool):
-        r = engine.submit(ids, params)
+    async def _stream(ids, params, chat: bool, adapter=None):
+        r = engine.submit(ids, params, adapter)
         sent = 0
         cid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         while True:
@@ -287,11 +296,14 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
 
 def build_default(model: str = "tiny", device: str | None = None, max_batch: int = 8, max_seq: int = 2048,
                   checkpoint: str | None = None, tokenizer_path: str | None = None, seed: int = 0,
-                  weights: str = "bf16", tp_group=None, kv_cache: str | None = None):
+                  weights: str = "bf16", tp_group=None, kv_cache: str | None = None, adapters: dict | None = None,
+                  max_loras: int | None = None, max_lora_rank: int = 16):
     """Engine + tokenizer.  ``tp_group``: this rank serves its tensor-parallel
     shard (mxllm/parallel/tensor.py) of the model; the full model is built (or
     loaded) on the rank's GPU, sliced and freed.  ``kv_cache``: "bf16" / "fp8" KV cache
-    (None: env MXLLM_KV_CACHE, default bf16; ``Engine(kv_dtype=...)``)."""
+    (None: env MXLLM_KV_CACHE, default bf16; ``Engine(kv_dtype=...)``).  ``adapters``: {name: PEFT
+    LoRA directory} served beside the base model (``max_loras`` table slots, default one per adapter,
+    each of rank <= ``max_lora_rank``); a request whose ``model`` is such a name runs on that adapter."""
     from ..data.tokenizer import get_tokenizer
     from ..models import build_model, tokenizer_path_for
 
@@ -320,8 +332,22 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
         quantize_model_fp8_(m)
     tok = get_tokenizer(cfg.vocab_size, tokenizer_path, cfg.bos_id, cfg.eos_id)
     eng = Engine(m, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id, getattr(tok, "eos_id", cfg.eos_id)),
-                 tp_group=tp_group, kv_dtype=kv_cache)
+                 tp_group=tp_group, kv_dtype=kv_cache,
+                 max_adapters=max(max_loras or 0, len(adapters or {})), max_lora_rank=max_lora_rank)
+    for name, path in (adapters or {}).items():
+        eng.load_adapter(name, path)
     return eng, tok
+
+
+def parse_lora_modules(items) -> dict:
+    """``NAME=DIR`` arguments of ``--lora`` -> {name: dir}."""
+    out = {}
+    for it in items or ():
+        name, sep, path = it.partition("=")
+        if not sep or not name or not path or name in out:
+            raise SystemExit(f"--lora takes NAME=DIR with distinct names, got {it!r}")
+        out[name] = path
+    return out
 
 
 def parse_args(argv=None):
@@ -344,6 +370,12 @@ def parse_args(argv=None):
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default=os.environ.get("MXLLM_KV_CACHE") or "bf16",
                     help="fp8: e4m3 KV cache, one byte per element and one f32 scale per (token, KV head) row "
                          "(head_dim 128; mxllm/serve/kvcache.py)")
+    ap.add_argument("--lora", action="append", default=[], metavar="NAME=DIR",
+                    help="serve a PEFT LoRA adapter directory under NAME beside the base model (repeatable); "
+                         "a request whose model is NAME runs on it")
+    ap.add_argument("--max-loras", type=int, default=None, help="adapter table slots (default: one per --lora)")
+    ap.add_argument("--max-lora-rank", type=int, default=16, choices=[8, 16, 32, 64],
+                    help="rank of the adapter tables; adapters of a lower rank are zero-padded")
     return ap.parse_args(argv)
 
 
@@ -361,7 +393,8 @@ def main(argv=None):
             raise SystemExit(f"--tp {a.tp} needs exactly {a.tp} ranks (torchrun --nproc-per-node={a.tp})")
         group = dist.group.WORLD
     eng, tok = build_default(a.model, None, a.max_batch, a.max_seq, a.checkpoint, a.tokenizer, weights=a.weights,
-                             tp_group=group, kv_cache=a.kv_cache)
+                             tp_group=group, kv_cache=a.kv_cache, adapters=parse_lora_modules(a.lora),
+                             max_loras=a.max_loras, max_lora_rank=a.max_lora_rank)
     if group is not None:
         eng.enable_tp_sync()
         if env.rank != 0:

@@ -93,6 +93,20 @@ def export_hf(run, trainer, rank):
         logging.info(f"Hugging Face checkpoint written to {run.save_hf}")
 
 
+def export_adapter(run, trainer, rank):
+    """--save-adapter DIR: the LoRA adapter alone as a PEFT directory (adapter_config.json +
+    adapter_model.safetensors), for multi-adapter serving (``--lora NAME=DIR``) or any PEFT tool."""
+    from mxllm.models import save_adapter
+
+    if run.finetune != "lora" or run.parallel == "zero3":
+        raise ValueError("--save-adapter needs a LoRA run (--finetune lora; ZeRO-3 trains the full model)")
+    trainer.params_ready()
+    if rank == 0:
+        save_adapter(trainer.model, run.save_adapter)
+        logging.info(f"LoRA adapter written to {run.save_adapter}")
+    runtime.barrier()
+
+
 def main(argv=None):
     setup_logging()
     code = 0
@@ -207,6 +221,8 @@ def main(argv=None):
             metrics.write(kind="final", step=total, master_bits_sum=s1, master_bits_wsum=s2, numel=m.numel())
         if run.save_hf:
             export_hf(run, trainer, rank)
+        if run.save_adapter:
+            export_adapter(run, trainer, rank)
         runtime.barrier()
     except Exception as e:
         logging.error(f"An error occurred in the main function: {e}")
