@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "bindings.h"
 #include <algorithm>
+#include <limits>
 #include <vector>
 
 namespace {
@@ -1062,23 +1063,6 @@ std::tuple<at::Tensor, at::Tensor> decode_attn_partials(const at::Tensor& q, con
   return {sp.ml, sp.po};
 }
 
-// y [M, N] = merge(part_ml, part_o) . W^T (decode o-projection with the split merge in the prologue)
-at::Tensor skinny_merge_linear(const at::Tensor& ml, const at::Tensor& po, const at::Tensor& w) {
-  MX_CHECK(ml.is_cuda() && ml.scalar_type() == at::kFloat && ml.is_contiguous() && ml.dim() == 4 && ml.size(3) == 2,
-           "part_ml f32 [M, Hq, nsplit, 2]");
-  MX_CHECK(po.is_cuda() && po.scalar_type() == at::kFloat && po.is_contiguous() && po.dim() == 4 &&
-               po.size(0) == ml.size(0) && po.size(1) == ml.size(1) && po.size(2) == ml.size(2) && po.size(3) == 128,
-           "part_o f32 [M, Hq, nsplit, 128]");
-  MX_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "w bf16 [N, K] rows");
-  const int64_t M = ml.size(0), K = ml.size(1) * 128, N = w.size(0);
-  MX_CHECK(w.size(1) == K, "w [N, Hq * 128]");
-  DevGuard g(w.device());
-  auto y = at::empty({M, N}, w.options());
-  MX_OK(mx_skinny_merge_gemm(ml.data_ptr<float>(), po.data_ptr<float>(), (int)ml.size(2), bf(w), w.stride(0), bfm(y),
-                             N, (int)M, (int)N, (int)K, cur_stream()));
-  return y;
-}
-
 at::Tensor sample(const at::Tensor& logits, double temperature, int64_t seed, int64_t step) {
   MX_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "logits [B, V] contiguous GPU");
   MX_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16/f32");
@@ -1210,71 +1194,111 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_rows(const at::Tensor& lo
 }  // namespace
 
 
-// ---------------------------------------------------------------- bf16 decode GEMM (serving)
-// y[M, N] = x[M, K] . w[N, K]^T for M <= 32 tokens: the weight-streaming HIP kernel
-// (csrc/kernels/skinny_gemm.hip).  Callers check the shape contract (mxllm/ops/linear.py).
+// ---------------------------------------------------------------- skinny decode GEMMs (serving)
+// y[M, N] = x[M, K] . w[N, K]^T for decode-sized M on the weight-streaming HIP kernels
+// (csrc/kernels/skinny_gemm.hip; fp8 weights: fp8_gemm.hip).  The helpers check what the ops are handed
+// (type, rank, device) before anything is allocated; which shapes and strides a kernel takes is
+// mx::sk_takes (csrc/kernels/skinny_args.h), asked by the launcher before it enqueues anything.
+// a 2-D bf16 row view (unit inner stride, any row stride) on `dev`
+static void sk_rows(const char* op, const char* name, const at::Tensor& t, const at::Device& dev) {
+  MX_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == at::kBFloat16 && t.dim() == 2 && t.stride(1) == 1, op,
+           ": ", name, " must be bf16 [rows, cols] GPU rows with a unit inner stride, on one device with the others");
+}
+static bool sk_ints(int64_t M, int64_t N, int64_t K) {
+  const int64_t lim = std::numeric_limits<int>::max();
+  return M <= lim && N <= lim && K <= lim;
+}
+// The operands every op shares, M rows of K (x [M, K], M >= 1, unless the op builds them) against w [N, K]
+// on one device: entry, X, W, M, N, K of the description
+static mx::SkLaunch sk_fill(const char* op, mx::SkEntry entry, const at::Tensor* x, const at::Tensor& w,
+                            const at::Device& dev, int64_t M, int64_t K) {
+  if (x) sk_rows(op, "x", *x, dev);
+  sk_rows(op, "w", w, dev);
+  MX_CHECK(w.size(1) == K && (!x || M >= 1) && sk_ints(M, w.size(0), K), op, ": ", M, " rows of ", K, " against w ",
+           w.sizes());
+  mx::SkLaunch L{};
+  L.entry = entry, L.W = {w.data_ptr(), w.stride(0)}, L.M = (int)M, L.N = (int)w.size(0), L.K = (int)K;
+  if (x) L.X = {x->data_ptr(), x->stride(0)};
+  return L;
+}
+static mx::SkLaunch sk_fill(const char* op, mx::SkEntry entry, const at::Tensor& x, const at::Tensor& w) {
+  MX_CHECK(x.dim() == 2, op, ": x must be [M, K]");
+  return sk_fill(op, entry, &x, w, x.device(), x.size(0), x.size(1));
+}
+// The RMSNorm prologue's operands into L.na: gamma [K], optionally delta [M, K] rows.  Returns the new
+// residual: h + delta (allocated here, written by the kernel), h itself without delta.
+static at::Tensor sk_norm(const char* op, mx::SkLaunch& L, const at::Tensor& h, const c10::optional<at::Tensor>& delta,
+                          const at::Tensor& gamma, double eps) {
+  MX_CHECK(gamma.device() == h.device() && gamma.scalar_type() == at::kBFloat16 && gamma.is_contiguous() &&
+               gamma.numel() == L.K, op, ": gamma must be contiguous bf16 [K] on h's device");
+  L.na.gamma = bf(gamma);
+  L.na.eps = (float)eps;
+  if (!delta.has_value() || !delta->defined()) return h;
+  sk_rows(op, "delta", *delta, h.device());
+  MX_CHECK(delta->size(0) == L.M && delta->size(1) == L.K, op, ": delta must have h's shape");
+  at::Tensor h_out = at::empty({L.M, L.K}, h.options());
+  L.na.delta = bf(*delta), L.na.ldd = delta->stride(0), L.na.h_out = bfm(h_out);
+  return h_out;
+}
+// The RoPE / KV-append epilogue's operands into L.rp (q: by the caller), as rope_append checks them
+static void sk_rope(const char* op, mx::SkLaunch& L, const at::Tensor& h, const at::Tensor& cosb, const at::Tensor& sinb,
+                    const at::Tensor& pos, const c10::optional<at::Tensor>& slots, at::Tensor& k_cache,
+                    at::Tensor& v_cache, int64_t Hq, int64_t Hkv, const c10::optional<at::Tensor>& block_table) {
+  MX_CHECK(Hq > 0 && Hkv > 0 && sk_ints(Hq, Hkv, 0), op, ": Hq, Hkv");
+  check_kv_pools(k_cache, v_cache, at::kBFloat16, 128, h.device(), Hkv, op);
+  for (const at::Tensor* t : {&cosb, &sinb})
+    MX_CHECK(t->device() == h.device() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
+                 t->size(1) == 64, op, ": cos / sin must be contiguous float32 [positions, 64] on h's device");
+  MX_CHECK(pos.defined(), op, ": pos");
+  const int32_t* pp = check_rows_i32(pos, h.device(), L.M, op, "pos");
+  const int32_t* sl = check_rows_i32(slots, h.device(), L.M, op, "slots");
+  const KvPages pg = kv_pages(block_table, k_cache);
+  L.rp = {cosb.data_ptr<float>(), sinb.data_ptr<float>(), pp, sl, nullptr, bfm(k_cache), bfm(v_cache), (int)Hq,
+          (int)Hkv, (int)k_cache.size(2), pg.bt, pg.maxb};
+}
+// rc of a launcher that was handed L: -1 is sk_takes' refusal (nothing was launched), > 0 a HIP error
+static void sk_launched(const char* op, int rc, const mx::SkLaunch& L) {
+  MX_CHECK(rc != -1, op, ": the kernel does not take this call (mx::sk_takes, csrc/kernels/skinny_args.h): M ", L.M,
+           ", N ", L.N, ", K ", L.K, ", row strides x ", L.X.ld, ", w ", L.W.ld, ", y ", L.Y.ld, ", delta ", L.na.ldd);
+  TORCH_CHECK(rc == 0, "mxllm kernel launch failed (", op, ") rc=", rc, " ", hipGetErrorString((hipError_t)rc));
+}
+// y [M, cols] allocated like `t` (under the caller's device guard), the launch, its report
+static at::Tensor sk_run(const char* op, mx::SkLaunch& L, const at::Tensor& t, int64_t cols) {
+  auto y = at::empty({L.M, cols}, t.options());
+  L.Y = {y.data_ptr(), cols};
+  sk_launched(op, mx_skinny(L, cur_stream()), L);
+  return y;
+}
+
 at::Tensor skinny_linear(const at::Tensor& x, const at::Tensor& w) {
-  MX_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "x: bf16 [M, K] rows");
-  MX_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "w: bf16 [N, K] rows");
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  MX_CHECK(w.size(1) == K && M >= 1 && M <= 32 && N % 16 == 0 && K % 512 == 0 && x.stride(0) % 8 == 0 &&
-               w.stride(0) % 8 == 0, "skinny_linear shape contract");
+  mx::SkLaunch L = sk_fill("skinny_linear", mx::SK_PLAIN, x, w);
   DevGuard g(x.device());
-  auto y = at::empty({M, N}, x.options());
-  MX_OK(mx_skinny_gemm(bf(x), x.stride(0), bf(w), w.stride(0), bfm(y), N, (int)M, (int)N, (int)K, cur_stream()));
-  return y;
+  return sk_run("skinny_linear", L, x, L.N);
 }
 
-// y[M, F] = swiglu(x[M, K] . w[2F, K]^T) for M <= 32 tokens, w = [gate; up] rows: the decode
-// MLP's first projection with SwiGLU in the GEMM epilogue (csrc/kernels/skinny_gemm.hip).
+// y[M, F] = swiglu(x . w^T), w = [gate; up] [2F, K] rows: the decode MLP's first projection with the
+// SwiGLU in the GEMM epilogue
 at::Tensor skinny_linear_swiglu(const at::Tensor& x, const at::Tensor& w) {
-  MX_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "x: bf16 [M, K] rows");
-  MX_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "w: bf16 [2F, K] rows");
-  const int64_t M = x.size(0), K = x.size(1), F = w.size(0) / 2;
-  MX_CHECK(w.size(1) == K && w.size(0) == 2 * F && M >= 1 && M <= 32 && F % 8 == 0 && K % 512 == 0 &&
-               x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, "skinny_linear_swiglu shape contract");
+  mx::SkLaunch L = sk_fill("skinny_linear_swiglu", mx::SK_SWIGLU, x, w);
   DevGuard g(x.device());
-  auto y = at::empty({M, F}, x.options());
-  MX_OK(mx_skinny_gemm_swiglu(bf(x), x.stride(0), bf(w), w.stride(0), bfm(y), F, (int)M, (int)F, (int)K,
-                              cur_stream()));
-  return y;
+  return sk_run("skinny_linear_swiglu", L, x, L.N / 2);
 }
 
-// Decode rows (M <= 4): y = rmsnorm(h + delta) . w^T with the RMSNorm (and residual add) in the
-// GEMM prologue (csrc/kernels/skinny_gemm.hip NORM); swiglu: w = [gate; up], y = silu(g) * u.
-// Returns (y, h + delta) — the new residual is h itself when delta is absent.
+// Decode rows: y = rmsnorm(h + delta) . w^T with the RMSNorm (and residual add) in the GEMM prologue;
+// swiglu: w = [gate; up], y = silu(g) * u.  Returns (y, h + delta) -- the new residual is h itself
+// when delta is absent.
 std::tuple<at::Tensor, at::Tensor> skinny_norm_linear(const at::Tensor& h, const c10::optional<at::Tensor>& delta,
                                                       const at::Tensor& gamma, double eps, const at::Tensor& w,
                                                       bool swiglu) {
-  MX_CHECK(h.is_cuda() && h.scalar_type() == at::kBFloat16 && h.dim() == 2 && h.stride(1) == 1, "h: bf16 [M, K] rows");
-  MX_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "w: bf16 [N, K] rows");
-  const int64_t M = h.size(0), K = h.size(1), N = w.size(0);
-  MX_CHECK(gamma.is_cuda() && gamma.scalar_type() == at::kBFloat16 && gamma.is_contiguous() && gamma.numel() == K,
-           "gamma: bf16 [K]");
-  MX_CHECK(w.size(1) == K && M >= 1 && M <= 4 && M * K <= 32768 && N % 16 == 0 && K % 512 == 0 &&
-               h.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && (!swiglu || N % 16 == 0),
-           "skinny_norm_linear shape contract");
-  const uint16_t* dp = nullptr;
-  int64_t ldd = 0;
-  at::Tensor h_out = h;
-  if (delta.has_value() && delta->defined()) {
-    const at::Tensor& d = *delta;
-    MX_CHECK(d.is_cuda() && d.scalar_type() == at::kBFloat16 && d.dim() == 2 && d.size(0) == M && d.size(1) == K &&
-                 d.stride(1) == 1 && d.stride(0) % 8 == 0, "delta: bf16 [M, K] rows");
-    dp = bf(d);
-    ldd = d.stride(0);
-    h_out = at::empty({M, K}, h.options());
-  }
+  mx::SkLaunch L = sk_fill("skinny_norm_linear", mx::SK_NORM, h, w);
+  L.swiglu = swiglu ? 1 : 0;
   DevGuard g(h.device());
-  const int64_t Ny = swiglu ? N / 2 : N;
-  auto y = at::empty({M, Ny}, h.options());
-  MX_OK(mx_skinny_norm_gemm(bf(h), h.stride(0), dp, ldd, bf(gamma), (float)eps, dp ? bfm(h_out) : nullptr, bf(w),
-                            w.stride(0), bfm(y), Ny, (int)M, (int)N, (int)K, swiglu ? 1 : 0, cur_stream()));
-  return {y, h_out};
+  at::Tensor h_out = sk_norm("skinny_norm_linear", L, h, delta, gamma, eps);
+  return {sk_run("skinny_norm_linear", L, h, swiglu ? L.N / 2 : L.N), h_out};
 }
 
 // Decode QKV projection with the RoPE / KV-cache append in the GEMM epilogue and, when gamma is
-// given, the (residual-add +) RMSNorm in its prologue (csrc/kernels/skinny_gemm.hip ROPE / NORM).
+// given, the (residual-add +) RMSNorm in its prologue (delta counts only then).
 // Returns (q [M, Hq, 128] rotated, new residual); K/V rows land in the caches at (slot, pos).
 std::tuple<at::Tensor, at::Tensor> skinny_qkv_rope(const at::Tensor& h, const c10::optional<at::Tensor>& delta,
                                                    const c10::optional<at::Tensor>& gamma, double eps,
@@ -1282,64 +1306,51 @@ std::tuple<at::Tensor, at::Tensor> skinny_qkv_rope(const at::Tensor& h, const c1
                                                    const at::Tensor& pos, const c10::optional<at::Tensor>& slots,
                                                    at::Tensor& k_cache, at::Tensor& v_cache, int64_t Hq, int64_t Hkv,
                                                    const c10::optional<at::Tensor>& block_table) {
-  MX_CHECK(h.is_cuda() && h.scalar_type() == at::kBFloat16 && h.dim() == 2 && h.stride(1) == 1, "h: bf16 [M, K] rows");
-  MX_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "w: bf16 [N, K] rows");
-  const int64_t M = h.size(0), K = h.size(1);
-  const bool norm = gamma.has_value() && gamma->defined();
-  MX_CHECK(w.size(0) == (Hq + 2 * Hkv) * 128 && w.size(1) == K && M >= 1 && M <= (norm ? 4 : 16) && K % 512 == 0 &&
-               (!norm || M * K <= 32768) && h.stride(0) % 8 == 0 && w.stride(0) % 8 == 0,
-           "skinny_qkv_rope shape contract");
-  MX_CHECK(cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
-               sinb.is_contiguous() && cosb.size(-1) == 64, "cos/sin f32 [max_pos, 64]");
-  MX_CHECK(pos.scalar_type() == at::kInt && pos.numel() == M, "pos int32 [M]");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
-  MX_CHECK(k_cache.size(1) == Hkv && k_cache.size(3) == 128 && k_cache.is_contiguous() && v_cache.is_contiguous(),
-           "caches [slots, Hkv, max_seq, 128]");
-  const int32_t* sl = nullptr;
-  if (slots.has_value() && slots->defined()) {
-    MX_CHECK(slots->scalar_type() == at::kInt && slots->numel() == M, "slots int32 [M]");
-    sl = slots->data_ptr<int32_t>();
-  }
-  const uint16_t* dp = nullptr;
-  int64_t ldd = 0;
-  at::Tensor h_out = h;
-  if (norm && delta.has_value() && delta->defined()) {
-    const at::Tensor& d = *delta;
-    MX_CHECK(d.is_cuda() && d.scalar_type() == at::kBFloat16 && d.dim() == 2 && d.size(0) == M && d.size(1) == K &&
-                 d.stride(1) == 1 && d.stride(0) % 8 == 0, "delta: bf16 [M, K] rows");
-    dp = bf(d);
-    ldd = d.stride(0);
-    h_out = at::empty({M, K}, h.options());
-  }
-  if (norm)
-    MX_CHECK(gamma->scalar_type() == at::kBFloat16 && gamma->is_contiguous() && gamma->numel() == K, "gamma bf16 [K]");
+  mx::SkLaunch L = sk_fill("skinny_qkv_rope", mx::SK_ROPE, h, w);
+  sk_rope("skinny_qkv_rope", L, h, cosb, sinb, pos, slots, k_cache, v_cache, Hq, Hkv, block_table);
+  L.norm = gamma.has_value() && gamma->defined();
   DevGuard g(h.device());
-  auto q = at::empty({M, Hq, 128}, h.options());
-  const KvPages pg = kv_pages(block_table, k_cache);
-  MX_OK(mx_skinny_rope_gemm(bf(h), h.stride(0), norm ? 1 : 0, dp, ldd, norm ? bf(*gamma) : nullptr, (float)eps,
-                            dp ? bfm(h_out) : nullptr, bf(w), w.stride(0), cosb.data_ptr<float>(),
-                            sinb.data_ptr<float>(), pos.data_ptr<int32_t>(), sl, bfm(q), bfm(k_cache),
-                            bfm(v_cache), (int)Hq, (int)Hkv, (int)k_cache.size(2), pg.bt, pg.maxb, (int)M, (int)K, cur_stream()));
+  at::Tensor h_out = L.norm ? sk_norm("skinny_qkv_rope", L, h, delta, *gamma, eps) : h;
+  auto q = at::empty({L.M, Hq, 128}, h.options());
+  L.rp.q = bfm(q);
+  sk_launched("skinny_qkv_rope", mx_skinny(L, cur_stream()), L);
   return {q, h_out};
+}
+
+// y [M, N] = merge(part_ml, part_o) . w^T: the decode o-projection with the split merge of
+// decode_attn_partials in its prologue
+at::Tensor skinny_merge_linear(const at::Tensor& ml, const at::Tensor& po, const at::Tensor& w) {
+  MX_CHECK(ml.is_cuda() && ml.scalar_type() == at::kFloat && ml.is_contiguous() && ml.dim() == 4 && ml.size(3) == 2,
+           "skinny_merge_linear: part_ml f32 [M, Hq, nsplit, 2]");
+  MX_CHECK(po.device() == ml.device() && po.scalar_type() == at::kFloat && po.is_contiguous() && po.dim() == 4 &&
+               po.size(0) == ml.size(0) && po.size(1) == ml.size(1) && po.size(2) == ml.size(2) && po.size(3) == 128,
+           "skinny_merge_linear: part_o f32 [M, Hq, nsplit, 128]");
+  mx::SkLaunch L = sk_fill("skinny_merge_linear", mx::SK_MERGE, nullptr, w, ml.device(), ml.size(0), ml.size(1) * 128);
+  MX_CHECK(sk_ints(ml.size(2), 0, 0), "skinny_merge_linear: nsplit");
+  L.mg = {ml.data_ptr<float>(), po.data_ptr<float>(), (int)ml.size(2)};
+  DevGuard g(w.device());
+  return sk_run("skinny_merge_linear", L, w, L.N);
 }
 
 // ---------------------------------------------------------------- fp8 weights (serving)
 // y[M, N] = x[M, K] . (scale[:, None] * q[N, K])^T ; q: e4m3 codes (uint8), scale f32 [N].
-// M <= 32: the fused weight-streaming kernel; otherwise dequantise to bf16 and run the
-// hipBLASLt GEMM.  mxllm/serve/quant.py calls this only up to SMALL_M (8) tokens and
-// routes larger calls to the fp8 x fp8 hipBLASLt GEMM.
+// Calls the fused weight-streaming kernel takes (mx::sk_takes, SK_W8) run on it; the others
+// dequantise to bf16 and run the hipBLASLt GEMM.  mxllm/serve/quant.py calls this only up to
+// SMALL_M (8) tokens and routes larger calls to the fp8 x fp8 hipBLASLt GEMM.
 at::Tensor w8_linear(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale) {
-  MX_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "x: bf16 [M, K] rows");
+  sk_rows("w8_linear", "x", x, x.device());
   MX_CHECK(q.is_cuda() && q.scalar_type() == at::kByte && q.dim() == 2 && q.is_contiguous(), "q: uint8 [N, K]");
   check_f32(scale, "scale");
   const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
   MX_CHECK(q.size(1) == K && scale.numel() == N, "w8_linear shapes");
   DevGuard g(x.device());
-  if (M <= 32 && N % 16 == 0 && K % 512 == 0 && x.stride(0) % 8 == 0) {
-    auto y = at::empty({M, N}, x.options());
-    MX_OK(mx_w8a16_gemm(bf(x), x.stride(0), q.data_ptr<uint8_t>(), scale.data_ptr<float>(), bfm(y), N, (int)M,
-                        (int)N, (int)K, cur_stream()));
+  auto y = at::empty({M, N}, x.options());
+  mx::SkLaunch L{};
+  L.entry = mx::SK_W8, L.X = {x.data_ptr(), x.stride(0)}, L.W = {q.data_ptr(), K}, L.Y = {y.data_ptr(), N};
+  L.M = (int)M, L.N = (int)N, L.K = (int)K, L.scale = scale.data_ptr<float>();
+  if (M == 0 || (sk_ints(M, N, K) && mx::sk_takes(L))) {  // no rows: an empty launch
+    sk_launched("w8_linear", mx_w8a16_gemm(bf(x), x.stride(0), q.data_ptr<uint8_t>(), L.scale, bfm(y), N, L.M, L.N,
+                                           L.K, cur_stream()), L);
     return y;
   }
   auto w = at::empty({N, K}, x.options());

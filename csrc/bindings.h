@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "kernels/gemm8_args.h"
+#include "kernels/skinny_args.h"
 
 extern "C" {
 // attn_bwd.hip
@@ -157,21 +158,9 @@ int mx_sample_rows(const void* logits, int is_bf16, int64_t* out, int B, int V, 
                    const float* top_ps, const int32_t* top_ks, const int64_t* seeds, const int32_t* steps,
                    hipStream_t stream);
 
-// skinny_gemm.hip
-int mx_skinny_gemm(const uint16_t* x, int64_t ldx, const uint16_t* w, int64_t ldw, uint16_t* y, int64_t ldy,
-                   int M, int N, int K, hipStream_t stream);
-int mx_skinny_gemm_swiglu(const uint16_t* x, int64_t ldx, const uint16_t* w, int64_t ldw, uint16_t* y,
-                          int64_t ldy, int M, int F, int K, hipStream_t stream);
-int mx_skinny_rope_gemm(const uint16_t* h, int64_t ldh, int norm, const uint16_t* delta, int64_t ldd,
-                        const uint16_t* gamma, float eps, uint16_t* h_out, const uint16_t* w, int64_t ldw,
-                        const float* cosb, const float* sinb, const int32_t* pos, const int32_t* slots, uint16_t* q,
-                        uint16_t* kc, uint16_t* vc, int Hq, int Hkv, int max_seq, const int32_t* bt, int maxb, int M,
-                        int K, hipStream_t stream);
-int mx_skinny_merge_gemm(const float* ml, const float* po, int nsplit, const uint16_t* w, int64_t ldw, uint16_t* y,
-                         int64_t ldy, int M, int N, int K, hipStream_t stream);
-int mx_skinny_norm_gemm(const uint16_t* h, int64_t ldh, const uint16_t* delta, int64_t ldd, const uint16_t* gamma,
-                        float eps, uint16_t* h_out, const uint16_t* w, int64_t ldw, uint16_t* y, int64_t ldy, int M,
-                        int N, int K, int swiglu, hipStream_t stream);
+// skinny_gemm.hip (operand rules of every entry: mx::sk_takes, kernels/skinny_args.h; the same
+// rules hold for mx_w8a16_gemm above)
+int mx_skinny(const mx::SkLaunch& L, hipStream_t stream);
 
 // xgmi.hip (called from runtime/xgmi_comm.cpp)
 int mx_xgmi_allreduce(uint32_t* const* flags, float* const* data, const float* in, float* out, int n,

@@ -5,32 +5,12 @@
 #pragma once
 
 #include "common.h"
+#include "skinny_args.h"  // SkNorm, SkRope, SkMerge: the kernel arguments of these pieces
 
 namespace mx {
 
 // the same expression as the SwiGLU kernels (elementwise.hip sigmoid_f): bit-identical outputs
 __device__ __forceinline__ float dfuse_silu(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-
-struct SkNorm {
-  const uint16_t* delta;  // [M, K] sub-block output added to the residual (nullptr: plain RMSNorm)
-  int64_t ldd;
-  const uint16_t* gamma;  // [K]
-  uint16_t* h_out;        // [M, K] (row stride K): h + delta, written by workgroup 0
-  float eps;
-};
-
-struct SkRope {
-  const float* cosb;     // [max_pos, 64]
-  const float* sinb;
-  const int32_t* pos;    // [M] position of the new token
-  const int32_t* slots;  // [M] cache slot (nullptr: row index)
-  uint16_t* q;           // [M, Hq, 128]
-  uint16_t* kc;          // [slots, Hkv, max_seq, 128], or paged [blocks, Hkv, block, 128]
-  uint16_t* vc;
-  int Hq, Hkv, max_seq;  // max_seq: the cache's sequence dimension (the block size when paged)
-  const int32_t* bt;     // paged: block table [slots, maxb] (nullptr: contiguous)
-  int maxb;
-};
 
 // Weight row of channel c (0..15) of workgroup blk in the paired layouts:
 //  SWO : 8 gate rows blk*8 .. +7 and the matching up rows F + blk*8 .. +7;
@@ -99,16 +79,8 @@ __device__ __forceinline__ void dfuse_norm_rows(const uint16_t* __restrict__ X, 
   __syncthreads();
 }
 
-// Split-K decode attention partials (decode.hip decode_attn_*: per (row, q-head, split) the
-// running max / sum in part_ml [M, Hq, nsplit, 2] and the unnormalised output in part_o
-// [M, Hq, nsplit, 128]) merged into the attention output rows xs [M, Hq * 128] (LDS) -- the
-// o-projection GEMM's X -- with decode_combine_kernel's arithmetic and order (same bits).
-struct SkMerge {
-  const float* ml;
-  const float* po;
-  int nsplit;
-};
-
+// Split-K decode attention partials (SkMerge) merged into the attention output rows xs [M, Hq * 128]
+// (LDS) -- the o-projection GEMM's X -- with decode_combine_kernel's arithmetic and order (same bits).
 __device__ __forceinline__ void dfuse_merge_rows(int M, int K, const SkMerge& mg, uint16_t* xs) {
   const int ns = mg.nsplit;
   for (int e = threadIdx.x * 8; e < M * K; e += blockDim.x * 8) {

@@ -186,12 +186,13 @@ __global__ void __launch_bounds__(256) quant_rows_e4m3_kernel(const uint16_t* __
 using namespace mx;
 
 // X [M, K] bf16 (row stride ldx), Q [N, K] e4m3 codes, scale [N] f32 (per output channel),
-// Y [M, N] bf16 (row stride ldy).  Requires M in 1..32, N % 16 == 0, K % 512 == 0,
-// ldx a multiple of 8, ldy of 4.
+// Y [M, N] bf16 (row stride ldy).  Which calls are taken: mx::sk_takes, SK_W8 (skinny_args.h).
 extern "C" int mx_w8a16_gemm(const uint16_t* x, int64_t ldx, const uint8_t* q, const float* scale, uint16_t* y,
                              int64_t ldy, int M, int N, int K, hipStream_t stream) {
   if (M <= 0) return 0;
-  if (M > 32 || N % 16 || K % 512 || ldx % 8 || ldy % 4 || ldx < K || ldy < N) return -1;
+  SkLaunch L{};
+  L.entry = SK_W8, L.X = {x, ldx}, L.W = {q, K}, L.Y = {y, ldy}, L.M = M, L.N = N, L.K = K, L.scale = scale;
+  if (!sk_takes(L)) return -1;
   // two channel groups per wave for 6..16 tokens when that still leaves >= 256 workgroups
   // (70B fp8 decode step, one group -> two: 22.0 -> 21.1 ms at 8 tokens, but 18.5 -> 19.3 ms
   // at 4; archive/profiles/r1g_fp8_decode_ab.md), and for 4..5 tokens on the long-K projections

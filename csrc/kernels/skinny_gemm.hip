@@ -190,108 +190,65 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const uint16_t* __rest
 
 using namespace mx;
 
-// y = rmsnorm(h [+ delta]) . W^T (or with the SwiGLU epilogue: W = [gate; up], y [M, N/2]) for
-// M <= 4 decode rows: the RMSNorm in the GEMM prologue (see NORM above).  h [M, K] (row stride
-// ldh), delta [M, K] (row stride ldd) or nullptr, gamma [K]; h_out [M, K] (row stride K) gets
-// h + delta when delta is given.  Requires M * K <= 32768 (64 KiB of LDS), K % 512 == 0.
-// Decode QKV projection with the RoPE / KV-cache append in the epilogue (see ROPE above), and
-// optionally the RMSNorm in the prologue (h, delta, gamma as mx_skinny_norm_gemm; norm = 0: X = h
-// as is, any M <= 16).  w [(Hq + 2 Hkv) * 128, K]; q out [M, Hq, 128].
-extern "C" int mx_skinny_rope_gemm(const uint16_t* h, int64_t ldh, int norm, const uint16_t* delta, int64_t ldd,
-                                   const uint16_t* gamma, float eps, uint16_t* h_out, const uint16_t* w, int64_t ldw,
-                                   const float* cosb, const float* sinb, const int32_t* pos, const int32_t* slots,
-                                   uint16_t* q, uint16_t* kc, uint16_t* vc, int Hq, int Hkv, int max_seq,
-                                   const int32_t* bt, int maxb, int M, int K, hipStream_t stream) {
-  if (M <= 0) return 0;
-  const int N = (Hq + 2 * Hkv) * 128;
-  if (M > (norm ? 4 : 16) || (norm && (int64_t)M * K > 32768) || K % 512 || ldh % 8 || ldd % 8 || ldw % 8 ||
-      ldh < K || ldw < K || (norm && delta && (ldd < K || !h_out)))
-    return -1;
-  const SkRope rp{cosb, sinb, pos, slots, q, kc, vc, Hq, Hkv, max_seq, bt, maxb};
-  if (norm) {
-    const SkNorm na{delta, ldd, gamma, h_out, eps};
-    skinny_gemm_kernel<1, 1, false, true, true><<<N / 16, 512, (size_t)M * K * 2, stream>>>(
-        h, ldh, w, ldw, nullptr, 0, M, K, 0, na, rp);
-  } else {
-    skinny_gemm_kernel<1, 1, false, false, true><<<N / 16, 512, 0, stream>>>(h, ldh, w, ldw, nullptr, 0, M, K, 0,
-                                                                               SkNorm{}, rp);
-  }
-  return (int)hipGetLastError();
-}
-
-// y[M, N] = merge(split partials) . W^T: the decode o-projection with decode.hip's split-K
-// attention merge (decode_combine_kernel) in its prologue -- every workgroup rebuilds the
-// attention output rows [M, Hq * 128] in LDS from part_ml [M, Hq, nsplit, 2] / part_o
-// [M, Hq, nsplit, 128] (same bits as the combine kernel).  Saves the combine launch of every
-// layer.  M <= 4, M * K <= 32768, K = Hq * 128 (% 512), N % 16 == 0.
-extern "C" int mx_skinny_merge_gemm(const float* ml, const float* po, int nsplit, const uint16_t* w, int64_t ldw,
-                                    uint16_t* y, int64_t ldy, int M, int N, int K, hipStream_t stream) {
-  if (M <= 0) return 0;
-  if (M > 4 || (int64_t)M * K > 32768 || N % 16 || K % 512 || ldw % 8 || ldy % 4 || ldw < K || ldy < N ||
-      nsplit < 1)
-    return -1;
-  const SkMerge mg{ml, po, nsplit};
-  skinny_gemm_kernel<1, 1, false, false, false, true><<<N / 16, 512, (size_t)M * K * 2, stream>>>(
-      nullptr, 0, w, ldw, y, ldy, M, K, 0, SkNorm{}, SkRope{}, mg);
-  return (int)hipGetLastError();
-}
-
-extern "C" int mx_skinny_norm_gemm(const uint16_t* h, int64_t ldh, const uint16_t* delta, int64_t ldd,
-                                   const uint16_t* gamma, float eps, uint16_t* h_out, const uint16_t* w,
-                                   int64_t ldw, uint16_t* y, int64_t ldy, int M, int N, int K, int swiglu,
-                                   hipStream_t stream) {
-  if (M <= 0) return 0;
-  if (M > 4 || (int64_t)M * K > 32768 || N % 16 || K % 512 || ldh % 8 || ldd % 8 || ldw % 8 || ldy % 4 ||
-      ldh < K || ldw < K || (delta && (ldd < K || !h_out)))
-    return -1;
-  const SkNorm na{delta, ldd, gamma, h_out, eps};
-  const size_t lds = (size_t)M * K * 2;
-  if (swiglu) {
-    const int Fh = N / 2;
-    if (Fh % 8 || ldy < Fh) return -1;
-    skinny_gemm_kernel<1, 1, true, true><<<Fh / 8, 512, lds, stream>>>(h, ldh, w, ldw, y, ldy, M, K, Fh, na);
-  } else {
-    if (ldy < N) return -1;
-    skinny_gemm_kernel<1, 1, false, true><<<N / 16, 512, lds, stream>>>(h, ldh, w, ldw, y, ldy, M, K, 0, na);
-  }
-  return (int)hipGetLastError();
-}
-
-// X [M, K] bf16 (row stride ldx), W [N, K] bf16 (row stride ldw), Y [M, N] bf16 (row stride
-// ldy).  Requires M in 1..32, N % 16 == 0, K % 512 == 0, ldx / ldw multiples of 8, ldy of 4.
-extern "C" int mx_skinny_gemm(const uint16_t* x, int64_t ldx, const uint16_t* w, int64_t ldw, uint16_t* y,
-                              int64_t ldy, int M, int N, int K, hipStream_t stream) {
-  if (M <= 0) return 0;
-  if (M > 32 || N % 16 || K % 512 || ldx % 8 || ldw % 8 || ldy % 4 || ldx < K || ldw < K || ldy < N) return -1;
-  // MXLLM_SKINNY_NC: channel groups per workgroup (1, 2 or 4; default 1).  Two or four groups
-  // cut the X traffic but halve / quarter the workgroups; measured at the Llama 8B / 70B decode
-  // shapes they won only on the 8B qkv projection (archive/profiles/r2x_skinny_gemm.md)
-  static const int nc_env = [] {
-    const char* e = getenv("MXLLM_SKINNY_NC");
-    return e && *e ? atoi(e) : 0;
-  }();
-  int nc = nc_env ? nc_env : 1;
-  while (nc > 1 && (N % (16 * nc) || N / (16 * nc) < 128)) nc >>= 1;
+// The one launcher of the bf16 skinny GEMMs.  What a description may ask for -- shapes, strides,
+// pointers, per entry -- is mx::sk_takes (skinny_args.h) and nothing else: a refused description
+// returns -1 with nothing enqueued; M <= 0 is an empty launch (0).  Here: the template instance,
+// the grid and the dynamic LDS of each entry.
+extern "C" int mx_skinny(const SkLaunch& L, hipStream_t stream) {
+  if (L.M <= 0) return 0;
+  if (L.entry == SK_W8 || !sk_takes(L)) return -1;  // SK_W8: mx_w8a16_gemm (fp8_gemm.hip)
+  const uint16_t* x = static_cast<const uint16_t*>(L.X.p);
+  const uint16_t* w = static_cast<const uint16_t*>(L.W.p);
+  uint16_t* y = static_cast<uint16_t*>(const_cast<void*>(L.Y.p));
+  const int64_t ldx = L.X.ld, ldw = L.W.ld, ldy = L.Y.ld;
+  const int M = L.M, N = L.N, K = L.K;
+  const size_t lds = (size_t)M * K * 2;  // the X rows a NORM / MERGE prologue builds
+  switch (L.entry) {
+    case SK_ROPE:  // one workgroup per 8 rotation pairs of a head; no Y: q and the caches are in L.rp
+      if (L.norm)
+        skinny_gemm_kernel<1, 1, false, true, true><<<N / 16, 512, lds, stream>>>(x, ldx, w, ldw, nullptr, 0, M, K, 0,
+                                                                                  L.na, L.rp);
+      else
+        skinny_gemm_kernel<1, 1, false, false, true><<<N / 16, 512, 0, stream>>>(x, ldx, w, ldw, nullptr, 0, M, K, 0,
+                                                                                   SkNorm{}, L.rp);
+      break;
+    case SK_MERGE:  // no X operand: the rows come from the split partials in L.mg
+      skinny_gemm_kernel<1, 1, false, false, false, true><<<N / 16, 512, lds, stream>>>(
+          nullptr, 0, w, ldw, y, ldy, M, K, 0, SkNorm{}, SkRope{}, L.mg);
+      break;
+    case SK_NORM:
+      if (L.swiglu)
+        skinny_gemm_kernel<1, 1, true, true><<<N / 2 / 8, 512, lds, stream>>>(x, ldx, w, ldw, y, ldy, M, K, N / 2, L.na);
+      else
+        skinny_gemm_kernel<1, 1, false, true><<<N / 16, 512, lds, stream>>>(x, ldx, w, ldw, y, ldy, M, K, 0, L.na);
+      break;
+    case SK_PLAIN: {
+      // MXLLM_SKINNY_NC: channel groups per workgroup (1, 2 or 4; default 1).  Two or four groups
+      // cut the X traffic but halve / quarter the workgroups; measured at the Llama 8B / 70B decode
+      // shapes they won only on the 8B qkv projection (archive/profiles/r2x_skinny_gemm.md)
+      static const int nc_env = [] {
+        const char* e = getenv("MXLLM_SKINNY_NC");
+        return e && *e ? atoi(e) : 0;
+      }();
+      int nc = nc_env ? nc_env : 1;
+      while (nc > 1 && (N % (16 * nc) || N / (16 * nc) < 128)) nc >>= 1;
 #define SKG(MBV, NCV) skinny_gemm_kernel<MBV, NCV><<<N / (16 * NCV), 512, 0, stream>>>(x, ldx, w, ldw, y, ldy, M, K)
-  if (M <= 16) {
-    if (nc >= 4) SKG(1, 4); else if (nc == 2) SKG(1, 2); else SKG(1, 1);
-  } else {
-    if (nc >= 4) SKG(2, 4); else if (nc == 2) SKG(2, 2); else SKG(2, 1);
-  }
+      if (M <= 16) {
+        if (nc >= 4) SKG(1, 4); else if (nc == 2) SKG(1, 2); else SKG(1, 1);
+      } else {
+        if (nc >= 4) SKG(2, 4); else if (nc == 2) SKG(2, 2); else SKG(2, 1);
+      }
 #undef SKG
-  return (int)hipGetLastError();
-}
-
-// y[M, F] = silu(g) * u with [g | u] = x[M, K] . W[2F, K]^T, W = [gate; up] rows: the decode
-// MLP's gate|up projection with the SwiGLU in its epilogue.  Same contract as mx_skinny_gemm
-// with N = 2F, plus F % 8 == 0.
-extern "C" int mx_skinny_gemm_swiglu(const uint16_t* x, int64_t ldx, const uint16_t* w, int64_t ldw, uint16_t* y,
-                                     int64_t ldy, int M, int F, int K, hipStream_t stream) {
-  if (M <= 0) return 0;
-  if (M > 32 || F % 8 || K % 512 || ldx % 8 || ldw % 8 || ldy % 4 || ldx < K || ldw < K || ldy < F) return -1;
-  if (M <= 16)
-    skinny_gemm_kernel<1, 1, true><<<F / 8, 512, 0, stream>>>(x, ldx, w, ldw, y, ldy, M, K, F);
-  else
-    skinny_gemm_kernel<2, 1, true><<<F / 8, 512, 0, stream>>>(x, ldx, w, ldw, y, ldy, M, K, F);
+      break;
+    }
+    case SK_SWIGLU:  // one workgroup per 8 gate rows and their 8 up rows (F = N / 2)
+      if (M <= 16)
+        skinny_gemm_kernel<1, 1, true><<<N / 2 / 8, 512, 0, stream>>>(x, ldx, w, ldw, y, ldy, M, K, N / 2);
+      else
+        skinny_gemm_kernel<2, 1, true><<<N / 2 / 8, 512, 0, stream>>>(x, ldx, w, ldw, y, ldy, M, K, N / 2);
+      break;
+    default:
+      return -1;
+  }
   return (int)hipGetLastError();
 }

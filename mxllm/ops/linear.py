@@ -556,6 +556,47 @@ def normed_linear(x: torch.Tensor, h: torch.Tensor, nw: torch.Tensor, eps: float
     return _NormedLinearFn.apply(x, h, nw, eps, w)
 
 
+# ---------------------------------------------------------------- skinny decode GEMMs
+def sk_takes(entry: str, M: int, N: int, K: int, ldx: int = 0, ldw: int = 0, ldy: int = 0, *, x=1, w=1, y=1,
+             swiglu: bool = False, norm: bool = False, delta=0, ldd: int = 0, gamma=1, h_out=1, rope=None,
+             merge=None, scale=1) -> bool:
+    """Whether the skinny decode GEMM launchers (csrc/kernels/skinny_gemm.hip ``mx_skinny``, fp8_gemm.hip
+    ``mx_w8a16_gemm``) take a launch -- the mirror of ``mx::sk_takes`` (csrc/kernels/skinny_args.h, rule for
+    rule, in its order; tests/test_skinny_args.py runs both over one grid).  ``entry``: "plain", "swiglu",
+    "norm", "rope", "merge", "w8"; ld*: row strides in elements; a pointer (x, w, y, delta, gamma, h_out,
+    scale, and in ``rope`` = {Hq, Hkv, max_seq, bt, maxb, cosb, sinb, pos, q, kc, vc}, ``merge`` = {nsplit, ml,
+    po}) is a number, 0 = null; those the caller's op always supplies default to given."""
+    is_rope, is_merge, w8 = entry == "rope", entry == "merge", entry == "w8"
+    norm = entry == "norm" or (is_rope and bool(norm))
+    swiglu = entry == "swiglu" or (entry == "norm" and bool(swiglu))
+    if entry not in ("plain", "swiglu", "norm", "rope", "merge", "w8"):
+        return False
+    if not w or (not is_merge and not x) or (not is_rope and not y):
+        return False
+    if K % 512 or M > (4 if norm or is_merge else 16 if is_rope else 32) or ((norm or is_merge) and M * K > 32768):
+        return False
+    if not is_merge and (ldx % 8 or ldx < K):
+        return False
+    if not w8 and (ldw % 8 or ldw < K):
+        return False
+    if not is_rope and (N % 16 or ldy % 4 or ldy < (N // 2 if swiglu else N)):
+        return False
+    if (entry == "norm" or is_rope) and ldd % 8:
+        return False
+    if norm and (not gamma or (delta and (ldd < K or not h_out))):
+        return False
+    if is_rope:
+        r = rope.get
+        if r("Hq", 0) <= 0 or r("Hkv", 0) <= 0 or r("max_seq", 0) <= 0 or N != (r("Hq") + 2 * r("Hkv")) * 128:
+            return False
+        if not all(r(p, 1) for p in ("cosb", "sinb", "pos", "q", "kc", "vc")) or (r("bt", 0) and r("maxb", 0) <= 0):
+            return False
+    if is_merge and (not merge.get("ml", 1) or not merge.get("po", 1) or merge["nsplit"] < 1):
+        return False
+    return not w8 or bool(scale)
+
+
+# What is dispatch policy and not the kernels' contract.
 # decode-sized GEMMs (bf16, no autograd) on the weight-streaming HIP kernel
 # (csrc/kernels/skinny_gemm.hip) where it beat hipBLASLt inside the decode step
 # (bench/serve_bench.py A/B, archive/profiles/r2x_skinny_gemm.md): one token row for every projection
@@ -563,23 +604,44 @@ def normed_linear(x: torch.Tensor, h: torch.Tensor, nw: torch.Tensor, eps: float
 # projections; the 70B ones lost at 4 rows).  MXLLM_SKINNY_M=0 keeps every GEMM on hipBLASLt.
 SKINNY_M = int(os.environ.get("MXLLM_SKINNY_M", "8"))
 _SKINNY_SMALL_W = 128 << 20
+# rows up to which the RMSNorm runs in the decode GEMM's prologue (every workgroup recomputes the
+# rows): measured same box, 8B decode batch 1 3.607 -> 3.479 ms and 70B 26.22 -> 24.98 ms, but batch 4
+# 3.83 -> 4.04 ms (archive/profiles/r2s3_decode_ab/); the kernel takes up to 4
+NORM_M = int(os.environ.get("MXLLM_NORM_FUSED_M", "2"))
+
+
+def _skinny_takes(entry: str, x2: torch.Tensor, w: torch.Tensor, *, swiglu: bool = False, norm: bool = False,
+                  gamma=None, delta=None, rope=None) -> bool:
+    """The policy above (row counts, the small-weight rule, no autograd), then the operands' form (bf16 row
+    views on the GPU; ``norm``: the RMSNorm prologue's gamma and optional delta), then ``sk_takes`` on the numbers."""
+    M, N = (x2.shape[0] if x2.dim() == 2 else 0), w.shape[0]
+    if not 0 < M <= (min(NORM_M, SKINNY_M) if norm else SKINNY_M) or (w.requires_grad and torch.is_grad_enabled()):
+        return False
+    if M > 1 and N * w.shape[1] > _SKINNY_SMALL_W:
+        return False
+    rows = (x2, w) if delta is None else (x2, w, delta)
+    if not (x2.is_cuda and use_native(x2) and x2.shape[1] == w.shape[1]
+            and all(t.dtype == torch.bfloat16 and t.stride(1) == 1 for t in rows)):
+        return False
+    if gamma is not None and (gamma.dtype != torch.bfloat16 or not gamma.is_contiguous()):
+        return False
+    if delta is not None and (not norm or delta.shape != x2.shape):
+        return False
+    return sk_takes(entry, M, N, x2.shape[1], x2.stride(0), w.stride(0), N // 2 if swiglu or entry == "swiglu" else N,
+                    swiglu=swiglu, norm=norm, delta=delta is not None, ldd=0 if delta is None else delta.stride(0),
+                    rope=rope)
 
 
 def _skinny_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
-    K, M = x2.shape[1], x2.shape[0]
-    if M > 1 and w.shape[0] * K > _SKINNY_SMALL_W:
-        return False
-    return (M <= SKINNY_M and x2.is_cuda and x2.dtype == torch.bfloat16
-            and w.dtype == torch.bfloat16 and K % 512 == 0 and w.shape[0] % 16 == 0 and x2.stride(1) == 1
-            and x2.stride(0) % 8 == 0 and w.stride(1) == 1 and w.stride(0) % 8 == 0 and use_native(x2))
+    return _skinny_takes("plain", x2, w)
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     if w.requires_grad and torch.is_grad_enabled():
         return _LinearFn.apply(x, w)
-    if SKINNY_M > 0 and x.shape[-1] == w.shape[1] and x.numel() // max(x.shape[-1], 1) <= SKINNY_M:
+    if x.shape[-1] == w.shape[1] and 0 < x.numel() // max(x.shape[-1], 1) <= SKINNY_M:
         x2 = x.reshape(-1, x.shape[-1])
-        if x2.shape[0] > 0 and _skinny_ok(x2, w):
+        if _skinny_ok(x2, w):
             return native().skinny_linear(x2, w).view(*x.shape[:-1], w.shape[0])
     return F.linear(x, w)
 
@@ -589,33 +651,22 @@ def linear_swiglu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor | None:
     ``w = [gate; up]`` [2F, K] (csrc/kernels/skinny_gemm.hip SWO variant: the SwiGLU in
     the GEMM epilogue, bit-identical to the GEMM + SwiGLU kernels).  None when the fused
     kernel does not take the call (the caller then runs the two ops)."""
-    if SKINNY_M <= 0 or x.dim() != 2 or (w.requires_grad and torch.is_grad_enabled()):
-        return None
-    if x.shape[1] != w.shape[1] or w.shape[0] % 16 or not 0 < x.shape[0] <= SKINNY_M:
-        return None
-    if not _skinny_ok(x, w):
-        return None
-    return native().skinny_linear_swiglu(x, w)
+    return native().skinny_linear_swiglu(x, w) if _skinny_takes("swiglu", x, w) else None
 
 
-# rows up to which the RMSNorm runs in the decode GEMM's prologue (every workgroup recomputes the
-# rows): measured same box, 8B decode batch 1 3.607 -> 3.479 ms and 70B 26.22 -> 24.98 ms, but batch 4
-# 3.83 -> 4.04 ms (archive/profiles/r2s3_decode_ab/); the kernel takes up to 4
-NORM_M = int(os.environ.get("MXLLM_NORM_FUSED_M", "2"))
+def _qkv_rope_takes(h, w, cos, sin, k_cache, v_cache, Hq: int, Hkv: int, norm: bool, gamma=None, delta=None) -> bool:
+    if not (k_cache.dim() == 4 and k_cache.shape[-1] == 128 and k_cache.dtype == torch.bfloat16
+            and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+            and k_cache.is_contiguous() and v_cache.is_contiguous()):
+        return False
+    return _skinny_takes("rope", h, w, norm=norm, gamma=gamma, delta=delta,
+                         rope={"Hq": Hq, "Hkv": Hkv, "max_seq": k_cache.shape[2]})
 
 
 def qkv_rope_ok(h: torch.Tensor, w: torch.Tensor, cos, sin, k_cache, v_cache, Hq: int, Hkv: int,
                 norm: bool) -> bool:
     """Whether :func:`qkv_rope_linear` takes these shapes (``norm``: with the RMSNorm prologue)."""
-    if SKINNY_M <= 0 or h.dim() != 2 or (w.requires_grad and torch.is_grad_enabled()):
-        return False
-    M, K = h.shape
-    if not 0 < M <= (min(NORM_M, SKINNY_M) if norm else SKINNY_M) or (norm and M * K > 32768):
-        return False
-    if w.shape != ((Hq + 2 * Hkv) * 128, K) or k_cache.shape[-1] != 128 or k_cache.dtype != torch.bfloat16:
-        return False
-    return bool(_skinny_ok(h, w) and cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-                and k_cache.is_contiguous() and v_cache.is_contiguous())
+    return _qkv_rope_takes(h, w, cos, sin, k_cache, v_cache, Hq, Hkv, norm)
 
 
 def qkv_rope_linear(delta, h: torch.Tensor, gamma, eps: float, w: torch.Tensor, cos, sin, pos, slots, k_cache,
@@ -625,12 +676,7 @@ def qkv_rope_linear(delta, h: torch.Tensor, gamma, eps: float, w: torch.Tensor, 
     RMSNorm in its prologue; ``gamma`` None: ``h`` is already normalised; ``block_table``:
     paged caches (mxllm/serve/kvcache.py).  Returns
     (q [M, Hq, 128] rotated, new residual) or None when the fused kernel does not take the call."""
-    if not qkv_rope_ok(h, w, cos, sin, k_cache, v_cache, Hq, Hkv, gamma is not None):
-        return None
-    norm = gamma is not None
-    if norm and (gamma.dtype != torch.bfloat16 or not gamma.is_contiguous()):
-        return None
-    if delta is not None and (not norm or delta.shape != h.shape or delta.stride(1) != 1 or delta.stride(0) % 8):
+    if not _qkv_rope_takes(h, w, cos, sin, k_cache, v_cache, Hq, Hkv, gamma is not None, gamma, delta):
         return None
     return native().skinny_qkv_rope(h, delta, gamma, float(eps), w, cos, sin, pos, slots, k_cache, v_cache, Hq, Hkv,
                                     block_table)
@@ -643,17 +689,16 @@ def norm_linear(delta: torch.Tensor | None, h: torch.Tensor, gamma: torch.Tensor
     the RMSNorm kernel + decode GEMM); with ``swiglu`` w = [gate; up] and the first output is
     silu(g) * u.  ``delta`` None: plain RMSNorm, the residual is ``h``.  None when the fused
     kernel does not take the call."""
-    if SKINNY_M <= 0 or h.dim() != 2 or (w.requires_grad and torch.is_grad_enabled()):
-        return None
-    M, K = h.shape
-    if not 0 < M <= min(NORM_M, SKINNY_M) or M * K > 32768 or h.stride(1) != 1 or w.shape[1] != K or w.shape[0] % 16:
-        return None
-    if gamma.dtype != torch.bfloat16 or not gamma.is_contiguous() or not _skinny_ok(h, w):
-        return None
-    if delta is not None and (delta.shape != h.shape or delta.dtype != h.dtype or delta.stride(1) != 1
-                              or delta.stride(0) % 8):
+    if not _skinny_takes("norm", h, w, swiglu=bool(swiglu), norm=True, gamma=gamma, delta=delta):
         return None
     return native().skinny_norm_linear(h, delta, gamma, float(eps), w, bool(swiglu))
+
+
+def merge_linear_ok(M: int, K: int, w: torch.Tensor) -> bool:
+    """Whether ``skinny_merge_linear`` (the o-projection with decode attention's split merge in its
+    prologue) takes M rows of K = heads * 128 against ``w`` [N, K]."""
+    return w.shape[1] == K and w.stride(1) == 1 and sk_takes("merge", M, w.shape[0], K, ldw=w.stride(0), ldy=w.shape[0],
+                                                             merge={"nsplit": 1})
 
 
 def lora_linear(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, b: torch.Tensor, splits: Sequence[int],

@@ -524,8 +524,7 @@ class Engine:
             if q is not None:  # RoPE and the cache append already done by the QKV GEMM
                 wo = m.layers[i].wo
                 K = q.shape[1] * 128  # this rank's heads (tensor parallel: a shard)
-                if (merge and type(wo) is FusedLinear and wo.lora_r == 0 and wo.weight.shape[0] % 16 == 0
-                        and K % 512 == 0 and B * K <= 32768 and wo.weight.shape[1] == K):
+                if merge and type(wo) is FusedLinear and wo.lora_r == 0 and ops.merge_linear_ok(B, K, wo.weight):
                     # partials only: the split merge runs in the o-projection's prologue
                     return ops.native().decode_attn_partials(q, self.kv.k[i], self.kv.v[i], pos, sl, max_len,
                                                              1.0 / math.sqrt(c.head_dim), 1, bt)
@@ -551,7 +550,8 @@ class Engine:
                 r = ops.qkv_rope_linear(delta, h, gamma, c.norm_eps, *rope)
                 if r is not None:
                     return r
-            if not ops.qkv_rope_ok(h, rope[0], rope[1], rope[2], rope[5], rope[6], rope[7], rope[8], False):
+            if not ops.qkv_rope_ok(h, layer.wqkv.weight, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i],
+                                   Hq=c.n_heads, Hkv=c.n_kv_heads, norm=False):
                 return None
             if delta is None:
                 xn = ops.rms_norm(h, gamma, c.norm_eps)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from mxllm.ops import decode as dops
+from mxllm.ops.linear import sk_takes
 from mxllm.serve.quant import dequantize_e4m3
 from tests import _parity as P
 from tests import test_decode_exact_gpu as TD
@@ -90,7 +91,7 @@ class RefDecode:
 
     def skinny_merge_linear(self, ml, po, w):
         M, Hq, ns, _ = ml.shape
-        if M > 4 or M * Hq * 128 > 32768 or w.shape[0] % 16:
+        if not sk_takes("merge", M, w.shape[0], Hq * 128, ldw=w.stride(0), ldy=w.shape[0], merge={"nsplit": ns}):
             raise RuntimeError("skinny_merge_linear: refused")
         m = ml[..., 0]
         wgt = torch.where(torch.isfinite(m), torch.exp2(m - m.amax(-1, keepdim=True)), torch.zeros_like(m))
@@ -315,26 +316,59 @@ def test_rejects_one_cache_row_outside_the_append_target_overwritten():
 
 
 # =========================================================================== decode GEMMs: reference ops
-def _contract(ok):
-    if not ok:
-        raise RuntimeError("shape contract")
+def _asked(op, entry, x, w, ldy=0, **kw):
+    """The refusal of the ops: whatever ``mxllm.ops.linear.sk_takes`` (the mirror of the launchers' one check)
+    refuses, and 2-D rows with a unit inner stride, M >= 1."""
+    rows = all(t.dim() == 2 and t.stride(1) == 1 for t in (x, w)) and x.shape[0] >= 1 and x.shape[1] == w.shape[1]
+    if not (rows and sk_takes(entry, x.shape[0], w.shape[0], x.shape[1], x.stride(0), w.stride(0), ldy, **kw)):
+        raise RuntimeError(f"{op}: the kernel does not take this call")
 
 
-def _rows_ok(*ts):
-    return all(t is None or (t.stride(1) == 1 and t.stride(0) % 8 == 0) for t in ts)
+def _delta_kw(op, h, delta):
+    if delta is None:
+        return {}
+    if delta.shape != h.shape or delta.stride(1) != 1:
+        raise RuntimeError(f"{op}: delta must have h's shape")
+    return dict(delta=1, ldd=delta.stride(0))
+
+
+def _qkv_operands(h, gamma, cos, sin, pos, slots, kc, vc, Hkv, bt):
+    """The tensor checks of skinny_qkv_rope (csrc/bindings.cpp sk_rope, sk_norm), on whatever device h is on."""
+    def need(ok, what):
+        if not ok:
+            raise RuntimeError(f"skinny_qkv_rope: {what}")
+
+    dev, (M, K) = h.device, h.shape
+    for c in (kc, vc):
+        need(c.device == dev and c.dtype == BF16 and c.dim() == 4 and c.is_contiguous(), "K and V pools must be "
+             "contiguous bf16 [rows, Hkv, SEQ, D] on the query's device")
+    need(kc.shape[3] == 128 and kc.shape[1] == Hkv, "the pools' heads and last dimension")
+    need(vc.shape == kc.shape, "the K and V pools differ in shape")
+    for t in (cos, sin):
+        need(t.device == dev and t.dtype == F32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == 64,
+             "cos / sin must be contiguous float32 [positions, 64] on h's device")
+    for name, t in (("pos", pos), ("slots", slots)):
+        need(t is not None or name == "slots", name)
+        need(t is None or (t.device == dev and t.dtype == I32 and t.is_contiguous() and t.numel() == M),
+             f"{name} must be a contiguous int32 [B] tensor on the query's device")
+    if bt is not None:
+        need(bt.dtype == I32 and bt.dim() == 2 and bt.is_contiguous(), "block_table int32 [slots, max_blocks]")
+        need(kc.shape[2] % 256 == 0, "paged KV: the block size must be a multiple of 256 tokens")
+    if gamma is not None:
+        need(gamma.device == dev and gamma.dtype == BF16 and gamma.is_contiguous() and gamma.numel() == K,
+             "gamma must be contiguous bf16 [K] on h's device")
 
 
 class RefSkinny:
     """The contracts of the decode GEMMs in plain fp32 PyTorch (integers and selections: exact)."""
 
     def skinny_linear(self, x, w):
-        M, K = x.shape
-        _contract(1 <= M <= 32 and w.shape[0] % 16 == 0 and K % 512 == 0 and _rows_ok(x, w))
+        _asked("skinny_linear", "plain", x, w, w.shape[0])
         return (x.float() @ w.float().t()).to(BF16)
 
     def skinny_linear_swiglu(self, x, w):
         F = w.shape[0] // 2
-        _contract(1 <= x.shape[0] <= 32 and F % 8 == 0 and x.shape[1] % 512 == 0 and _rows_ok(x, w))
+        _asked("skinny_linear_swiglu", "swiglu", x, w, F)
         gu = (x.float() @ w.float().t()).to(BF16).float()
         return (torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]).to(BF16)
 
@@ -344,15 +378,18 @@ class RefSkinny:
         return (hf * torch.rsqrt(hf.pow(2).mean(-1, keepdim=True) + eps) * gamma.float()).to(BF16), hb
 
     def skinny_norm_linear(self, h, delta, gamma, eps, w, swiglu):
-        M, K = h.shape
-        _contract(1 <= M <= 4 and M * K <= 32768 and K % 512 == 0 and w.shape[0] % 16 == 0 and _rows_ok(h, delta, w))
+        if gamma.numel() != h.shape[1]:
+            raise RuntimeError("skinny_norm_linear: gamma")
+        _asked("skinny_norm_linear", "norm", h, w, w.shape[0] // 2 if swiglu else w.shape[0], swiglu=swiglu,
+               **_delta_kw("skinny_norm_linear", h, delta))
         xn, hb = self._norm(h, delta, gamma, eps)
         return (self.skinny_linear_swiglu(xn, w) if swiglu else self.skinny_linear(xn, w)), hb
 
     def skinny_qkv_rope(self, h, delta, gamma, eps, w, cos, sin, pos, slots, kc, vc, Hq, Hkv, bt=None):
-        M, K = h.shape
         norm = gamma is not None
-        _contract(1 <= M <= (4 if norm else 16) and K % 512 == 0 and _rows_ok(h, delta, w))
+        _qkv_operands(h, gamma, cos, sin, pos, slots, kc, vc, Hkv, bt)
+        _asked("skinny_qkv_rope", "rope", h, w, norm=norm, **(_delta_kw("skinny_qkv_rope", h, delta) if norm else {}),
+               rope=dict(Hq=Hq, Hkv=Hkv, max_seq=kc.shape[2], bt=bt is not None, maxb=0 if bt is None else bt.shape[1]))
         xn, hb = self._norm(h, delta, gamma, eps) if norm else (h, h)
         qkv = (xn.float() @ w.float().t()).to(BF16)
         return REF.rope_append(qkv, cos, sin, pos, slots, kc, vc, Hq, Hkv, 128, bt), hb
@@ -361,7 +398,7 @@ class RefSkinny:
         return dequantize_e4m3(q, scale).to(BF16)
 
     def w8_linear(self, x, q, scale):
-        if x.shape[0] > 32 or x.shape[1] % 512:  # dequantise to bf16 + GEMM
+        if not sk_takes("w8", x.shape[0], q.shape[0], x.shape[1], x.stride(0), ldy=q.shape[0]):  # dequantise + GEMM
             return TS.w8_fallback_products(x, q, scale)[0].to(BF16)
         y32 = TS.w8_products(x, q, torch.ones_like(scale))[0] * scale.float()
         return y32.to(BF16)
@@ -407,6 +444,17 @@ def test_gaussian_linear_cases(M, N, K):
 def test_linear_refusal_cases():
     TS.check_linear_refusals(RS.skinny_linear, CPU)
     TS.check_norm_refusals(RS.skinny_norm_linear, CPU)
+
+
+@pytest.mark.parametrize("op", TS.RULE_CHECKS)
+def test_refusals_by_rule_cases(op):
+    """The reference ops refuse exactly what the launchers' check refuses: they ask its mirror."""
+    TS.RULE_CHECKS[op](getattr(REF if op == "skinny_merge_linear" else RS, op), CPU)
+
+
+def test_qkv_rope_operand_cases():
+    TS.check_qkv_operands(RS.skinny_qkv_rope, CPU)
+    assert len({m for _, m, _ in TS.qkv_bad_operands(CPU)}) == 7  # pos, slots, cos / sin, pools, block_table, gamma, delta
 
 
 def test_channel_group_cases():

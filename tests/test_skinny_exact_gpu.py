@@ -147,11 +147,11 @@ def lin_expected(kind, M, N, K):
     return x, w, None, x.double() @ w.double().t()
 
 
-def check_linear(kind, M, N, K, run, dev, bound=None):
+def check_linear(kind, M, N, K, run, dev, bound=None, xpad=24, wpad=8):
     """``run(x, w) -> y``.  x: a row-strided view with NaN pad columns and NaN rows after row M - 1;
     W row-strided with NaN pads."""
     x, w, want, r64 = lin_expected(kind, M, N, K)
-    xd, wd = strided(x, 24, 3, dev), strided(w, 8, 0, dev)
+    xd, wd = strided(x, xpad, 3, dev), strided(w, wpad, 0, dev)
     y = run(xd, wd).cpu()
     name = f"{kind} M{M} N{N} K{K}"
     if want is not None:
@@ -218,12 +218,12 @@ def silu64(g):
     return g / (1.0 + torch.exp(-g))
 
 
-def check_swiglu(M, F, K, run, dev):
+def check_swiglu(M, F, K, run, dev, xpad=24, wpad=8):
     """g = x[m, pi(n)], u = x[m, pi(F + n)] exactly; y against fp64 silu(g) * u under SWIGLU_M."""
     x = finite_x(M, K, 3400 + 64 * M + F + K, extremes=False)
     pi = perm_map(2 * F, K)
     gu = select(x, pi).double()
-    y = run(strided(x, 24, 3, dev), strided(perm_weight(2 * F, K), 8, 0, dev)).cpu()
+    y = run(strided(x, xpad, 3, dev), strided(perm_weight(2 * F, K), wpad, 0, dev)).cpu()
     ref64 = silu64(gu[:, :F]) * gu[:, F:]
     assert_parity(y, ref64, P.SWIGLU_M, name=f"swiglu M{M} F{F} K{K}")
     return y, ref64
@@ -251,14 +251,14 @@ def norm_inputs(M, K, resid):
     return h, d, gamma, hb, xn64
 
 
-def check_norm_linear(M, K, resid, swiglu, run, dev):
+def check_norm_linear(M, K, resid, swiglu, run, dev, N=NORM_N, hpad=16, dpad=40, wpad=8):
     """``run(h, delta, gamma, eps, w, swiglu) -> (y, h_out)``.  y[m, n] is the normalised row element
     pi(n) (RMSNORM_Y against fp64), or silu(g) * u of two of them, each rounded to bf16 (SWIGLU_M)."""
     h, d, gamma, hb, xn64 = norm_inputs(M, K, resid)
-    pi = perm_map(NORM_N, K)
-    hd = strided(h, 16, 2, dev)
-    y, h_out = run(hd, strided(d, 40, 1, dev) if resid else None, gamma.to(dev), EPS,
-                   strided(perm_weight(NORM_N, K), 8, 0, dev), swiglu)
+    pi = perm_map(N, K)
+    hd = strided(h, hpad, 2, dev)
+    y, h_out = run(hd, strided(d, dpad, 1, dev) if resid else None, gamma.to(dev), EPS,
+                   strided(perm_weight(N, K), wpad, 0, dev), swiglu)
     name = f"norm M{M} K{K} resid{resid} swiglu{swiglu}"
     if resid:
         assert_exact(bits(h_out.cpu()), bits(hb), f"{name}: h + delta")
@@ -267,7 +267,7 @@ def check_norm_linear(M, K, resid, swiglu, run, dev):
     sel = xn64[:, pi]
     if swiglu:
         gu = sel.to(BF16).double()  # g and u are rounded to bf16 before the SwiGLU (skinny_gemm.hip SWO)
-        F = NORM_N // 2
+        F = N // 2
         assert_parity(y.cpu(), silu64(gu[:, :F]) * gu[:, F:], P.SWIGLU_M, name=name)
     else:
         assert_parity(y.cpu(), sel, P.RMSNORM_Y, name=name)
@@ -305,12 +305,27 @@ def qkv_id(c):
            f"{'paged' if paged else 'contig'}-{kind}"
 
 
-def check_qkv_rope(case, run, dev):
-    """``run(h, delta, gamma, eps, w, cos, sin, pos, slots, kc, vc, Hq, Hkv, bt) -> (q, h_out)``."""
+@functools.lru_cache(maxsize=4)
+def small_layout(M, Hkv, paged):
+    """The layout of the refusal tests: caches of 2 slots x 256 positions of random bits (the canary), rows on
+    alternating slots at distinct positions (0 and 255 included); paged: the same pools as two blocks of 256."""
+    g = _gen(3650 + 8 * M + Hkv + paged)
+    mid = 1 + torch.randperm(254, generator=g)
+    pos = torch.cat([torch.tensor([0]), mid[:max(M - 2, 0)], torch.tensor([255])])[:M].to(I32)
+    shape = (2, Hkv, 256, 128)
+    cos, sin = TD.ref.rope_tables(256, 128, TD.ROPE_THETA, None)
+    return dict(kc=TD.random_bits_cache(g, shape), vc=TD.random_bits_cache(g, shape), pos=pos,
+                slots=(torch.arange(M) % 2).to(I32), bt=torch.tensor([[1], [0]], dtype=I32) if paged else None,
+                cos=cos, sin=sin)
+
+
+def qkv_inputs(case, small=False):
+    """(layout, h, delta, gamma, w, the bf16 projection the rotation starts from, h + delta)."""
     M, Hq, Hkv, K, norm, resid, paged, kind = case
     N = (Hq + 2 * Hkv) * 128
     g = _gen(3600 + 64 * M + Hq + K + paged)
-    c = TD.append_layout(g, M, Hkv, 128, 300, paged, True)
+    c = small_layout(M, Hkv, paged) if small else TD.append_layout(g, M, Hkv, 128, 300, paged, True)
+    hb = None
     if norm:  # the projection selects from the bf16 rounding of the fp64 normalised row
         h, d, gamma, hb, xn64 = norm_inputs(M, K, resid)
         w = perm_weight(N, K)
@@ -323,18 +338,31 @@ def check_qkv_rope(case, run, dev):
     else:
         h, d, gamma, w = finite_x(M, K, 3602 + M, extremes=False), None, None, perm_weight(N, K)
         proj = select(h, perm_map(N, K))
+    return c, h, d, gamma, w, proj, hb
+
+
+def qkv_args(case, inp, dev, kc, vc, hpad=16, dpad=40, wpad=8):
+    """The op's arguments by name, in its order, on ``dev``."""
+    c, h, d, gamma, w = inp[:5]
+    return dict(h=strided(h, hpad, 2, dev), delta=strided(d, dpad, 1, dev) if d is not None else None,
+                gamma=TD._dev(gamma, dev), eps=EPS, w=strided(w, wpad, 0, dev), cos=c["cos"].to(dev),
+                sin=c["sin"].to(dev), pos=c["pos"].to(dev), slots=c["slots"].to(dev), kc=kc, vc=vc, Hq=case[1],
+                Hkv=case[2], bt=TD._dev(c["bt"], dev))
+
+
+def check_qkv_rope(case, run, dev, small=False, **pads):
+    """``run(h, delta, gamma, eps, w, cos, sin, pos, slots, kc, vc, Hq, Hkv, bt) -> (q, h_out)``."""
+    M, Hq, Hkv, K, norm, resid, paged, kind = case
+    inp = qkv_inputs(case, small)
     out = {}
 
     def go(kc, vc):
-        q, h_out = run(strided(h, 16, 2, dev), strided(d, 40, 1, dev) if d is not None else None,
-                       gamma.to(dev) if norm else None, EPS, strided(w, 8, 0, dev), c["cos"].to(dev), c["sin"].to(dev),
-                       c["pos"].to(dev), c["slots"].to(dev), kc, vc, Hq, Hkv, TD._dev(c["bt"], dev))
-        out["h"] = h_out
+        q, out["h"] = run(*qkv_args(case, inp, dev, kc, vc, **pads).values())
         return q
 
-    TD.check_append(qkv_id(case), c, proj, Hq, Hkv, 128, go, dev)
+    TD.check_append(qkv_id(case), inp[0], inp[5], Hq, Hkv, 128, go, dev)
     if norm and resid:
-        assert_exact(bits(out["h"].cpu()), bits(hb), f"{qkv_id(case)}: h + delta")
+        assert_exact(bits(out["h"].cpu()), bits(inp[6]), f"{qkv_id(case)}: h + delta")
 
 
 @pytest.mark.parametrize("case", QKV_CASES, ids=qkv_id)
@@ -428,7 +456,7 @@ def w8_case(kind, M, N, K):
     return x, q, scale
 
 
-def check_w8_linear(kind, M, N, K, run, dev):
+def check_w8_linear(kind, M, N, K, run, dev, xpad=24):
     """``run(x, q, scale) -> y``; x row-strided with NaN pads and NaN rows past M."""
     name = f"w8 {kind} M{M} N{N} K{K}"
     x, q, scale = w8_case(kind, M, N, K)
@@ -436,7 +464,7 @@ def check_w8_linear(kind, M, N, K, run, dev):
         r64 = w8_products(x, q, scale, f64=False)[0].double()
     else:
         r64 = w8_products(x, q, scale, f32=False)[1]
-    y = run(strided(x, 24, 3, dev), q.to(dev), scale.to(dev)).cpu()
+    y = run(strided(x, xpad, 3, dev), q.to(dev), scale.to(dev)).cpu()
     if kind == "int":
         assert_exact(bits(y), bits(r64.to(F32).to(BF16)), name)
     else:
@@ -521,6 +549,161 @@ def check_quant_rows(K, run, dev):
 @pytest.mark.parametrize("K", QUANT_K)
 def test_quant_rows_e4m3_bitwise(gpu, K):
     check_quant_rows(K, _ops().quant_rows_e4m3, gpu)
+
+
+# =========================================================================== the launchers' rules, one by one
+# mx::sk_takes (csrc/kernels/skinny_args.h) through the six ops.  Per rule: one call just inside, which passes
+# the op's exact check at that shape, and one just outside, which raises a RuntimeError naming the op
+# (w8_linear: runs the documented dequantise + GEMM fallback) -- at the smallest shapes on either side: K 512
+# against 768, N 16 against 24, the row limit against one more, (4, 8192) against (4, 8704) for the 64 KiB of
+# LDS, a row pad of 8 against 4.  Then a valid call passes again.  Not reachable through an op: the rules
+# on ldy (the op allocates y), rows shorter than K (a view's rows are as long as its width) and nsplit >= 1.
+def run_sides(op, check, base, rules, run, dev):
+    """Per (inside, outside) of ``rules``: ``check`` passes at the base with ``inside`` and raises, naming the op,
+    with ``outside``; at the end the base passes again."""
+    for inside, outside in rules:
+        check(run=run, dev=dev, **dict(base, **inside))
+        with pytest.raises(RuntimeError, match=op):
+            check(run=run, dev=dev, **dict(base, **outside))
+    check(run=run, dev=dev, **base)
+
+
+PADS_XW = [(dict(xpad=8), dict(xpad=4)), (dict(wpad=8), dict(wpad=4))]
+
+
+def check_rules_linear(run, dev):
+    rules = [(dict(M=32), dict(M=33)), (dict(N=16), dict(N=24)), (dict(K=512), dict(K=768))] + PADS_XW
+    run_sides("skinny_linear", check_linear, dict(kind="perm", M=4, N=16, K=512, xpad=8, wpad=8), rules, run, dev)
+
+
+def check_rules_swiglu(run, dev):
+    rules = [(dict(M=32), dict(M=33)), (dict(F=8), dict(F=12)), (dict(K=512), dict(K=768))] + PADS_XW
+    run_sides("skinny_linear_swiglu", check_swiglu, dict(M=4, F=8, K=512, xpad=8, wpad=8), rules, run, dev)
+
+
+PADS_HDW = [(dict(hpad=8), dict(hpad=4)), (dict(dpad=8), dict(dpad=4)), (dict(wpad=8), dict(wpad=4))]
+
+
+def check_rules_norm(run, dev):
+    rules = [(dict(M=4), dict(M=5)), (dict(K=8192), dict(K=8704)), (dict(N=16), dict(N=24)),
+             (dict(N=16, swiglu=True), dict(N=24, swiglu=True)), (dict(K=512), dict(K=768))] + PADS_HDW
+    base = dict(M=4, K=512, resid=True, swiglu=False, N=16, hpad=8, dpad=8, wpad=8)
+    run_sides("skinny_norm_linear", check_norm_linear, base, rules, run, dev)
+
+
+def check_qkv_refused(case, run, dev, match="skinny_qkv_rope", edit=None, **pads):
+    """The call raises and leaves both caches -- random bits, the canary -- bitwise as they were."""
+    inp = qkv_inputs(case, True)
+    c = inp[0]
+    kc, vc = c["kc"].to(dev, copy=True), c["vc"].to(dev, copy=True)
+    a = qkv_args(case, inp, dev, kc, vc, **pads)
+    if edit:
+        edit(a)
+    with pytest.raises(RuntimeError, match=match):
+        run(*a.values())
+    assert_exact(bits(kc.cpu()), bits(c["kc"]), f"{qkv_id(case)}: K cache after a refused call")
+    assert_exact(bits(vc.cpu()), bits(c["vc"]), f"{qkv_id(case)}: V cache after a refused call")
+
+
+def _qkv(M=4, K=512, norm=False, resid=False, paged=False):
+    return (M, 2, 1, K, norm, resid, paged, "perm")  # Hq 2, Hkv 1
+
+
+def check_rules_qkv(run, dev):
+    pads = dict(hpad=8, dpad=8, wpad=8)
+    nd = dict(norm=True, resid=True)
+    for inside, outside, pin, pout in [
+            (_qkv(M=16), _qkv(M=17), {}, {}),                                      # without the prologue
+            (_qkv(M=4, **nd), _qkv(M=5, **nd), {}, {}),                            # with it
+            (_qkv(K=8192, **nd), _qkv(K=8704, **nd), {}, {}),
+            (_qkv(M=16, K=8704), None, {}, {}),                                    # no LDS bound without it
+            (_qkv(K=512), _qkv(K=768), {}, {}), (_qkv(K=512, norm=True), _qkv(K=768, norm=True), {}, {}),
+            (_qkv(), _qkv(), {}, dict(hpad=4)), (_qkv(), _qkv(), {}, dict(wpad=4)),
+            (_qkv(**nd), _qkv(**nd), {}, dict(dpad=4))]:
+        check_qkv_rope(inside, run, dev, small=True, **dict(pads, **pin))
+        if outside is not None:
+            check_qkv_refused(outside, run, dev, **dict(pads, **pout))
+    # N = (Hq + 2 Hkv) * 128: the weight of two q-heads against Hq = 3
+    check_qkv_refused(_qkv(), run, dev, edit=lambda a: a.update(Hq=3), **pads)
+    check_qkv_rope(_qkv(**nd), run, dev, small=True, **pads)
+
+
+def check_merge_rule(M, Hq, N, wpad, run, dev):
+    """``run(ml, po, w) -> y``: the exact merge case of tests/test_decode_exact_gpu.py against the first N rows
+    of the identity, y = the merged row's first N elements."""
+    ml, po, ref64 = TD.merge_case(M, Hq, 1, True)
+    w = torch.eye(N, Hq * 128, dtype=BF16)
+    y = run(ml.to(dev), po.to(dev), strided(w, wpad, 0, dev)).cpu()
+    assert_exact(bits(y), bits(ref64[:, :N].to(F32).to(BF16)), f"merge M{M} Hq{Hq} N{N} wpad{wpad}")
+
+
+def check_rules_merge(run, dev):
+    rules = [(dict(M=4), dict(M=5)), (dict(Hq=64), dict(Hq=68)), (dict(N=16), dict(N=24)), (dict(Hq=4), dict(Hq=6)),
+             (dict(wpad=8), dict(wpad=4))]
+    run_sides("skinny_merge_linear", check_merge_rule, dict(M=4, Hq=4, N=16, wpad=8), rules, run, dev)
+
+
+def check_w8_outside(M, N, K, xpad, run, dev):
+    """A call the fp8 kernel does not take: the fallback's GEMM of the bf16-rounded weights, per element."""
+    x, q, scale = w8_case("gauss", M, N, K)
+    y = run(strided(x, xpad, 3, dev), q.to(dev), scale.to(dev)).cpu()
+    assert_parity(y, w8_fallback_products(x, q, scale)[1], P.W8_DEQ_Y, name=f"w8 fallback M{M} N{N} K{K} xpad{xpad}")
+
+
+def check_rules_w8(run, dev):
+    rules = [(dict(M=32), dict(M=33)), (dict(N=16), dict(N=24)), (dict(K=512), dict(K=768)), (dict(xpad=8), dict(xpad=4))]
+    base = dict(M=4, N=16, K=512, xpad=8)
+    for inside, outside in rules:
+        check_w8_linear("int", run=run, dev=dev, **dict(base, **inside))
+        check_w8_outside(run=run, dev=dev, **dict(base, **outside))
+    check_w8_linear("int", run=run, dev=dev, **base)
+
+
+RULE_CHECKS = dict(skinny_linear=check_rules_linear, skinny_linear_swiglu=check_rules_swiglu,
+                   skinny_norm_linear=check_rules_norm, skinny_qkv_rope=check_rules_qkv,
+                   skinny_merge_linear=check_rules_merge, w8_linear=check_rules_w8)
+
+
+@pytest.mark.parametrize("op", RULE_CHECKS)
+def test_refusals_by_rule(gpu, op):
+    RULE_CHECKS[op](getattr(_ops(), op), gpu)
+
+
+# --------------------------------------------------------------------------- skinny_qkv_rope's operands
+def qkv_bad_operands(dev):
+    """(case, the operand the message names, the edit of the valid arguments)."""
+    other = torch.device("cpu") if dev.type == "cuda" else torch.device("meta")  # not the device of h
+
+    def to(name, f):
+        return lambda a: a.update({name: f(a[name])})
+
+    return [("pos on another device", "pos", to("pos", lambda t: t.to(other))),
+            ("pos int64", "pos", to("pos", lambda t: t.long())),
+            ("pos a stride-2 view", "pos", to("pos", lambda t: torch.stack([t, t], 1)[:, 0])),
+            ("pos of M + 1", "pos", to("pos", lambda t: torch.cat([t, t[:1]]))),
+            ("slots on another device", "slots", to("slots", lambda t: t.to(other))),
+            ("slots of M - 1", "slots", to("slots", lambda t: t[:-1])),
+            ("cos on another device", "cos / sin", to("cos", lambda t: t.to(other))),
+            ("cos of width 32", "cos / sin", to("cos", lambda t: t[:, :32].contiguous())),
+            ("sin non-contiguous", "cos / sin", to("sin", lambda t: torch.cat([t, t], 1)[:, :64])),
+            ("v_cache of another shape", "pools", to("vc", lambda t: torch.cat([t, t[:1]]))),
+            ("k_cache 3-D", "pools", to("kc", lambda t: t[0])),
+            ("head_dim 64", "pools", lambda a: a.update(kc=a["kc"][..., :64].contiguous(), vc=a["vc"][..., :64].contiguous())),
+            ("block_table int64", "block_table", to("bt", lambda t: t.long())),
+            ("gamma of K - 8", "gamma", to("gamma", lambda t: t[:-8])),
+            ("delta of M + 1 rows", "delta", to("delta", lambda t: torch.cat([t, t[:1]])))]
+
+
+def check_qkv_operands(run, dev):
+    """Every operand check refuses before anything is written; then the valid call passes."""
+    case = _qkv(norm=True, resid=True, paged=True)
+    for name, match, edit in qkv_bad_operands(dev):
+        check_qkv_refused(case, run, dev, match=match, edit=edit)
+    check_qkv_rope(case, run, dev, small=True)
+
+
+def test_skinny_qkv_rope_operand_checks(gpu):
+    check_qkv_operands(_ops().skinny_qkv_rope, gpu)
 
 
 # =========================================================================== yardstick
