@@ -11,7 +11,9 @@
 #include <hip/hip_runtime.h>
 #include "bindings.h"
 #include <algorithm>
+#include <cstring>
 #include <limits>
+#include <mutex>
 #include <vector>
 
 namespace {
@@ -967,6 +969,82 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at:
   return out;
 }
 
+// ---------------------------------------------------------------- paged-KV prefill attention
+// Causal attention of query segments over the paged bf16 cache (csrc/kernels/prefill_paged.hip):
+// q [T, Hq, 128], pools [blocks, Hkv, blk, 128], block_table int32 [slots, maxb], segs int32 [nseg, 4]
+// = (first q row, n, slot, p0) -> out [T, Hq * 128]; rows outside every segment are not written.
+// The segments come from host lists: mx::pp_takes (kernels/prefill_paged_args.h) checks the host copy
+// before anything is enqueued, so a refused call writes nothing.  The device copy of the segment and
+// work tables is kept for the next call with the same segments (every layer of one prefill pass).
+at::Tensor prefill_attn_paged(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                              const at::Tensor& block_table, const at::Tensor& segs, double scale,
+                              const c10::optional<at::Tensor>& out) {
+  const char* op = "prefill_attn_paged";
+  MX_CHECK(q.is_cuda() && q.dim() == 3 && q.is_contiguous(), op, ": q must be a contiguous GPU tensor [T, Hq, D]");
+  MX_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
+               k_cache.is_contiguous() && v_cache.is_contiguous() && k_cache.device() == q.device() &&
+               v_cache.device() == q.device() && k_cache.scalar_type() == v_cache.scalar_type(),
+           op, ": K and V pools must be contiguous [blocks, Hkv, blk, D] tensors of one shape and type on q's device");
+  MX_CHECK(block_table.device() == q.device() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+               block_table.is_contiguous(),
+           op, ": block_table must be a contiguous int32 [slots, max_blocks] tensor on q's device");
+  MX_CHECK(segs.scalar_type() == at::kInt && segs.dim() == 2 && segs.size(1) == 4, op,
+           ": segs must be int32 [nseg, 4] = (first q row, n, slot, p0)");
+  MX_CHECK(k_cache.size(3) == q.size(2), op, ": the pools' last dimension is ", k_cache.size(3), ", q's is ", q.size(2));
+  const int64_t T = q.size(0), Hq = q.size(1), D = q.size(2);
+  if (out.has_value() && out->defined())
+    MX_CHECK(out->device() == q.device() && out->dim() == 2 && out->size(0) == T && out->size(1) == Hq * D &&
+                 out->stride(1) == 1,
+             op, ": out must be [T, Hq * D] rows on q's device");
+  const at::Tensor sh = segs.cpu().contiguous();
+  const int64_t nseg = sh.size(0);
+  DevGuard g(q.device());
+  at::Tensor o = out.has_value() && out->defined() ? *out : at::empty({T, Hq * D}, q.options());
+  if (nseg == 0 || T == 0) return o;
+  const auto* sp = reinterpret_cast<const mx::PpSeg*>(sh.data_ptr<int32_t>());
+
+  mx::PpLaunch L{};
+  L.q = q.data_ptr();
+  L.k_pool = k_cache.data_ptr();
+  L.v_pool = v_cache.data_ptr();
+  L.o = o.data_ptr();
+  L.bt = block_table.data_ptr<int32_t>();
+  L.segs_host = sp;
+  L.q_bf16 = q.scalar_type() == at::kBFloat16;
+  L.kv_bf16 = k_cache.scalar_type() == at::kBFloat16;
+  L.o_bf16 = o.scalar_type() == at::kBFloat16;
+  L.T = T, L.Hq = Hq, L.Hkv = k_cache.size(1), L.D = D;
+  L.blocks = k_cache.size(0), L.blk = k_cache.size(2), L.slots = block_table.size(0), L.maxb = block_table.size(1);
+  L.nseg = nseg, L.nwork = mx::pp_work_count(sp, nseg), L.ldo = o.stride(0);
+  // the check runs on placeholders of the two device tables first: nothing is uploaded for a refused call
+  L.segs = L.work = L.bt;
+  MX_CHECK(mx::pp_takes(L), op, ": the kernel does not take this call (mx::pp_takes, csrc/kernels/prefill_paged_args.h): T ",
+           T, ", Hq ", Hq, ", Hkv ", L.Hkv, ", D ", D, ", blk ", L.blk, ", slots ", L.slots, ", maxb ", L.maxb, ", ", nseg,
+           " segments");
+
+  static std::mutex mu;
+  static std::vector<int32_t> host_key;
+  static at::Tensor dev_tab;
+  at::Tensor tab;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<int32_t> key((size_t)(4 * nseg + 2 * L.nwork));
+    std::memcpy(key.data(), sp, sizeof(int32_t) * 4 * (size_t)nseg);
+    mx::pp_fill_work(sp, nseg, key.data() + 4 * nseg);
+    if (!dev_tab.defined() || dev_tab.device() != q.device() || key != host_key) {
+      at::Tensor ht = at::empty({(int64_t)key.size()}, at::TensorOptions().dtype(at::kInt));
+      std::memcpy(ht.data_ptr<int32_t>(), key.data(), sizeof(int32_t) * key.size());
+      dev_tab = ht.to(q.device());
+      host_key = std::move(key);
+    }
+    tab = dev_tab;
+  }
+  L.segs = tab.data_ptr<int32_t>();
+  L.work = L.segs + 4 * nseg;
+  MX_OK(mx_prefill_attn_paged(L, (float)scale, cur_stream()));
+  return o;
+}
+
 // ---------------------------------------------------------------- kv8: fp8 (e4m3) KV cache, head_dim 128
 // Pools of one layer: codes uint8 [rows, Hkv, SEQ, 128] and scales f32 [rows, Hkv, SEQ] for K and
 // for V (contiguous or paged like the bf16 caches).
@@ -1548,6 +1626,7 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("rope_append(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_cache, Tensor(b!) v_cache, int Hq, int Hkv, int D, Tensor? block_table=None) -> Tensor");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None, Tensor? counters=None) -> Tensor");
   m.def("decode_attn_partials(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> (Tensor, Tensor)");
+  m.def("prefill_attn_paged(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_table, Tensor segs, float scale, Tensor? out=None) -> Tensor");
   m.def("kv8_quant_rows(Tensor x) -> (Tensor, Tensor)");
   m.def("rope_append_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_codes, Tensor(b!) k_scale, Tensor(c!) v_codes, Tensor(d!) v_scale, int Hq, int Hkv, Tensor? block_table=None) -> Tensor");
   m.def("decode_attn_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> Tensor");
@@ -1614,6 +1693,7 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("decode_attn_partials", &decode_attn_partials);
   m.impl("skinny_merge_linear", &skinny_merge_linear);
   m.impl("decode_attn", &decode_attn);
+  m.impl("prefill_attn_paged", &prefill_attn_paged);
   m.impl("kv8_quant_rows", &kv8_quant_rows);
   m.impl("rope_append_kv8", &rope_append_kv8);
   m.impl("decode_attn_kv8", &decode_attn_kv8);

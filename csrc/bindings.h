@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "kernels/gemm8_args.h"
+#include "kernels/prefill_paged_args.h"
 #include "kernels/skinny_args.h"
 
 extern "C" {
@@ -137,6 +138,9 @@ int mx_peer_collective_light(int mode, int dtype, int wire, char* const* lbases,
 int mx_peer_collective(int mode, int dtype, char* const* bases, const void* in, void* out, int64_t n,
                        int64_t m, int rank, int world, int wgs, int slot_bytes, uint32_t* epochs, int* err,
                        long long timeout_ticks, hipStream_t stream);
+
+// prefill_paged.hip (operand rules: mx::pp_takes, kernels/prefill_paged_args.h)
+int mx_prefill_attn_paged(const mx::PpLaunch& L, float scale, hipStream_t stream);
 
 // rmsnorm.hip
 int mx_rmsnorm_fwd(const uint16_t* x, const uint16_t* res, const uint16_t* w, uint16_t* y,

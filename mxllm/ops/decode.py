@@ -2,12 +2,14 @@
 
 GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, their kv8
 forms over an fp8 KV cache, greedy / Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature),
-logits_proc.hip (sampling penalties, logit_bias, log-probabilities) and
-attn_fwd.hip for prefill.  CPU: reference implementations.
+logits_proc.hip (sampling penalties, logit_bias, log-probabilities),
+attn_fwd.hip for prefill and prefill_paged.hip for prefill chunks over the paged cache.
+CPU: reference implementations.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -48,6 +50,138 @@ def _kv_at(cache: torch.Tensor, bt, slot: int, p0: int, p1: int) -> torch.Tensor
         parts.append(_kv_at(cache, bt, slot, a, e))
         a = e
     return torch.cat(parts, 1)
+
+
+# ---------------------------------------------------------------- prefill chunks over the paged cache
+class PrefillPlan:
+    """The segments of one prefill pass, prepared once and reused by every layer: ``segs`` a list of
+    ``(row0, n, slot, p0)`` -- rows [row0, row0 + n) of the pass are positions [p0, p0 + n) of cache
+    slot ``slot`` -- over ``T`` rows.  Holds the per-row position / slot tensors ``rope_append``
+    reads, the int32 [nseg, 4] host table the attention kernel's binding checks, and (gather route)
+    a host copy of the block table."""
+
+    def __init__(self, segs, T: int, device, block_table: torch.Tensor | None = None):
+        self.segs = [tuple(int(x) for x in s) for s in segs]
+        self.T = int(T)
+        for row0, n, slot, p0 in self.segs:
+            if n <= 0 or row0 < 0 or row0 + n > self.T or p0 < 0 or slot < 0:
+                raise ValueError(f"bad prefill segment {(row0, n, slot, p0)} over {self.T} rows")
+        order = sorted(self.segs)
+        if any(b[0] < a[0] + a[1] for a, b in zip(order, order[1:])):
+            raise ValueError("prefill segments overlap")
+        self.table = torch.tensor(self.segs, dtype=torch.int32).reshape(-1, 4)
+        # all rows covered in order: one rope_append launch over the pass
+        self.dense = sum(s[1] for s in self.segs) == self.T
+        pos = torch.zeros(self.T, dtype=torch.int32)
+        slots = torch.zeros(self.T, dtype=torch.int32)
+        for row0, n, slot, p0 in self.segs:
+            pos[row0:row0 + n] = torch.arange(p0, p0 + n, dtype=torch.int32)
+            slots[row0:row0 + n] = slot
+        device = torch.device(device)
+        if device.type == "cuda":
+            pos, slots = pos.pin_memory().to(device, non_blocking=True), slots.pin_memory().to(device, non_blocking=True)
+        self.pos, self.slots = pos, slots
+        self.bt_host = block_table.cpu() if block_table is not None else None
+
+
+def prefill_paged_route(D: int, Hq: int, Hkv: int, blk: int, dtype) -> str:
+    """GPU route of ``prefill_attention_paged``: "hip" (csrc/kernels/prefill_paged.hip) where the
+    kernel takes the launch -- bf16, head_dim 128, whole GQA groups of at most 16, a block size
+    that is a multiple of 256 -- else "gather".  ``MXLLM_PREFILL_PAGED=hip|gather`` forces one;
+    a forced "hip" that the kernel does not take is an error, not a fall-back."""
+    env = os.environ.get("MXLLM_PREFILL_PAGED", "")
+    if env:
+        if env not in ("hip", "gather"):
+            raise ValueError(f"MXLLM_PREFILL_PAGED must be hip or gather, got {env!r}")
+        return env
+    takes = dtype == torch.bfloat16 and D == 128 and Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv <= 16 and blk % 256 == 0
+    return "hip" if takes else "gather"
+
+
+def paged_attention_gather(q: torch.Tensor, k_cache, v_cache, bt_host, segs, scale: float,
+                           out: torch.Tensor) -> torch.Tensor:
+    """The gather route of ``prefill_attention_paged`` (GPU, any head dim ``attn_fwd`` takes): per
+    segment ``(row0, n, slot, p0)`` the rows [0, p0 + n) of the slot are made contiguous (``_kv_at``
+    through the HOST block table) and fed to ``attn_fwd`` with Sk = p0 + n > S = n, whose causal
+    offset Sk - S is p0.  q [T, Hq, D] (rope_append's output) -> rows of ``out`` [T, Hq * D]."""
+    ops = native()
+    Hq, D = q.shape[1], q.shape[2]
+    for row0, n, slot, p0 in segs:
+        kk = _kv_at(k_cache, bt_host, slot, 0, p0 + n).contiguous().unsqueeze(0)
+        vv = _kv_at(v_cache, bt_host, slot, 0, p0 + n).contiguous().unsqueeze(0)
+        qs = q[row0:row0 + n].transpose(0, 1).contiguous().unsqueeze(0)  # [1, Hq, n, D]
+        o, _ = ops.attn_fwd(qs, kk, vv, True, scale)
+        out[row0:row0 + n] = o.view(n, Hq * D)
+    return out
+
+
+def prefill_attention_paged(qkv: torch.Tensor, cos, sin, k_cache, v_cache, block_table, segs, Hq: int, Hkv: int,
+                            D: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Prefill chunks over the paged KV cache.  qkv [T, NH*D]; ``segs`` a host list of
+    ``(row0, n, slot, p0)`` (or a ``PrefillPlan`` of it, built once per pass): rows
+    [row0, row0 + n) are positions [p0, p0 + n) of cache slot ``slot``.  RoPE and the cache append
+    of every segment row (``rope_append``, pos = p0 + t), then causal attention of each segment
+    over rows [0, p0 + n) of its slot, which now hold the chunk's own K/V: row t sees keys
+    0 .. p0 + t.  -> o [T, Hq*D]; rows outside every segment are not written (``out`` keeps them).
+
+    GPU routes (``prefill_paged_route``): "hip" -- one launch of the paged flash-attention kernel
+    for all segments; "gather" -- per segment, rows [0, p0 + n) made contiguous (``_kv_at``) and
+    ``attn_fwd`` with Sk > S (its causal offset Sk - S is p0).  CPU: the fp32 softmax expression."""
+    T = qkv.shape[0]
+    plan = segs if isinstance(segs, PrefillPlan) else PrefillPlan(segs, T, qkv.device)
+    if plan.T != T:
+        raise ValueError(f"the plan covers {plan.T} rows, qkv has {T}")
+    scale = 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty(T, Hq * D, dtype=qkv.dtype, device=qkv.device)
+    if not plan.segs:
+        return out
+    if use_native(qkv):
+        ops = native()
+        route = prefill_paged_route(D, Hq, Hkv, k_cache.shape[2], qkv.dtype)
+        qkv = qkv.contiguous()
+        if plan.dense:
+            q = ops.rope_append(qkv, cos, sin, plan.pos, plan.slots, k_cache, v_cache, Hq, Hkv, D, block_table)
+        else:  # rows in no segment are neither rotated nor appended
+            q = torch.empty(T, Hq, D, dtype=qkv.dtype, device=qkv.device)
+            for row0, n, _, _ in plan.segs:
+                q[row0:row0 + n] = ops.rope_append(qkv[row0:row0 + n], cos, sin, plan.pos[row0:row0 + n].contiguous(),
+                                                   plan.slots[row0:row0 + n].contiguous(), k_cache, v_cache, Hq, Hkv,
+                                                   D, block_table)
+        if route == "hip":
+            return ops.prefill_attn_paged(q, k_cache, v_cache, block_table, plan.table, scale, out)
+        if plan.bt_host is None:
+            plan.bt_host = block_table.cpu()
+        return paged_attention_gather(q, k_cache, v_cache, plan.bt_host, plan.segs, scale, out)
+    bt = block_table.cpu() if block_table is not None else None
+    x = qkv.view(T, Hq + 2 * Hkv, D).float()
+    for row0, n, slot, p0 in plan.segs:
+        c = cos[p0:p0 + n].view(n, 1, D // 2).float()
+        sn = sin[p0:p0 + n].view(n, 1, D // 2).float()
+
+        def rot(t):
+            t1, t2 = t[..., : D // 2], t[..., D // 2:]
+            return torch.cat([t1 * c - t2 * sn, t2 * c + t1 * sn], -1)
+
+        xs = x[row0:row0 + n]
+        qi = rot(xs[:, :Hq]).to(qkv.dtype).float()  # [n, Hq, D], rounded as rope_append stores it
+        ki = rot(xs[:, Hq:Hq + Hkv]).to(k_cache.dtype)
+        vi = qkv.view(T, Hq + 2 * Hkv, D)[row0:row0 + n, Hq + Hkv:].to(v_cache.dtype)
+        blk = k_cache.shape[2] if bt is not None else None
+        a = 0
+        while a < n:  # the chunk's own rows, block by block
+            e = n if blk is None else min(n, ((p0 + a) // blk + 1) * blk - p0)
+            _kv_at(k_cache, bt, slot, p0 + a, p0 + e).copy_(ki[a:e].transpose(0, 1))
+            _kv_at(v_cache, bt, slot, p0 + a, p0 + e).copy_(vi[a:e].transpose(0, 1))
+            a = e
+        kk = _kv_at(k_cache, bt, slot, 0, p0 + n).float().repeat_interleave(Hq // Hkv, 0)  # [Hq, L, D]
+        vv = _kv_at(v_cache, bt, slot, 0, p0 + n).float().repeat_interleave(Hq // Hkv, 0)
+        sc = torch.einsum("nhd,hld->hnl", qi, kk) * scale
+        key = torch.arange(p0 + n).view(1, 1, -1)
+        row = torch.arange(n).view(1, -1, 1)
+        sc = sc.masked_fill(key > row + p0, float("-inf"))
+        out[row0:row0 + n] = torch.einsum("hnl,hld->nhd", sc.softmax(-1), vv).reshape(n, Hq * D).to(out.dtype)
+    return out
 
 
 # ---------------------------------------------------------------- kv8: the fp8 (e4m3) KV cache

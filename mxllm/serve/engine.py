@@ -146,6 +146,8 @@ class Request:
     # one (logprob, [(token id, logprob), ...]) per output token when params.logprobs is set
     logprobs: list = field(default_factory=list)
     adapter: str | None = None  # name of a loaded LoRA adapter (Engine.load_adapter); None = the base model
+    cached_tokens: int = 0  # prompt tokens served from the prefix cache (Engine(prefix_cache=True))
+    prefilled: int = 0      # prompt positions whose K/V are in the cache (paged prefill: cached + computed chunks)
 
     def __post_init__(self):
         # any penalty / logit_bias / logprobs: the request takes the adjusted sampling path
@@ -156,7 +158,8 @@ class Engine:
     def __init__(self, model, max_batch: int = 8, max_seq: int = 4096, device=None, eos_ids=(),
                  use_graphs: bool | None = None, prefill_tokens: int = 16384, tp_group=None,
                  kv_pool_tokens: int | None = None, kv_block: int = 256, kv_dtype: str | None = None,
-                 max_adapters: int = 0, max_lora_rank: int = 16):
+                 max_adapters: int = 0, max_lora_rank: int = 16, prefix_cache: bool | None = None,
+                 prefill_chunk: int | None = None):
         """``tp_group``: serve a tensor-parallel shard (mxllm/parallel/tensor.py
         ``shard_llama`` / ``random_shard``) with the other ranks of the group;
         every rank of the group runs the same schedule (same submissions in the
@@ -172,11 +175,32 @@ class Engine:
         ``max_adapters`` > 0: serve that many LoRA adapters beside the base weights
         (``load_adapter``; a request names its adapter), each of rank <= ``max_lora_rank`` (8, 16,
         32 or 64).  The tables (mxllm/ops/lora_serve.py ``AdapterTables``) are allocated once; 0
-        allocates nothing and leaves every code path as it is without adapters."""
+        allocates nothing and leaves every code path as it is without adapters.
+        ``prefix_cache`` (None: env MXLLM_PREFIX_CACHE=1; needs ``kv_pool_tokens``): full 256-token
+        blocks of finished and running requests stay indexed by their token prefix and adapter
+        (mxllm/serve/kvcache.py); a request whose prompt starts with a cached chain shares those
+        blocks and prefills only the rest.  ``prefill_chunk`` = N (None: env MXLLM_PREFILL_CHUNK):
+        a step prefills at most N prompt tokens before the running batch gets its decode step, so a
+        long prompt no longer stalls streaming requests for its whole prefill.  With either option
+        every prefill runs through ``prefill_segments`` (``dops.prefill_attention_paged``: attention
+        of a chunk over the rows already in the block pool); with both off nothing changes.
+        Neither works with ``kv_dtype="fp8"`` or ``tp_group`` yet (ValueError).  Two new requests of
+        ONE admission pass that share a prefix both miss: blocks are registered when a prompt completes."""
         if max_adapters < 0:
             raise ValueError(f"max_adapters must be >= 0, got {max_adapters}")
         if max_adapters > 0 and tp_group is not None:
             raise ValueError("LoRA adapters are served by single-GPU engines (tp_group with max_adapters > 0)")
+        if prefix_cache is None:
+            prefix_cache = os.environ.get("MXLLM_PREFIX_CACHE", "0") not in ("", "0")
+        if prefill_chunk is None and os.environ.get("MXLLM_PREFILL_CHUNK"):
+            prefill_chunk = int(os.environ["MXLLM_PREFILL_CHUNK"])
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        self.prefix_cache = bool(prefix_cache)
+        self.prefill_chunk = prefill_chunk
+        self.paged_prefill = self.prefix_cache or prefill_chunk is not None  # every prefill through prefill_segments
+        if self.paged_prefill and tp_group is not None:
+            raise ValueError("prefix_cache / prefill_chunk are not supported under tensor parallelism (tp_group) yet")
         self.model = model
         self.tp = None
         if tp_group is not None:
@@ -221,9 +245,14 @@ class Engine:
         if kv_dtype == "fp8" and c.head_dim != 128:
             raise ValueError(f"the fp8 KV cache supports head_dim 128 only; this model has head_dim {c.head_dim}")
         self.kv_dtype = kv_dtype
+        if self.paged_prefill and kv_dtype == "fp8":
+            raise ValueError("prefix_cache / prefill_chunk are not supported over the fp8 KV cache yet")
+        if self.prefix_cache and kv_pool_tokens is None:
+            raise ValueError("prefix_cache needs the paged KV cache (kv_pool_tokens / MXLLM_KV_POOL_TOKENS)")
         self.kv = KVCache(c.n_layers, c.n_kv_heads, c.head_dim, dt, self.device, n_slots, self.max_seq,
                           pool_tokens=kv_pool_tokens, block=kv_block,
-                          scratch_slot=self.scratch_slot if self.use_graphs else None, kv_dtype=kv_dtype)
+                          scratch_slot=self.scratch_slot if self.use_graphs else None, kv_dtype=kv_dtype,
+                          prefix_cache=self.prefix_cache)
         # MXLLM_DECODE_COMBINE=fused: the split-K partials merge inside the attention launch (the
         # last workgroup of each (seq, kv-head) combines; these counters stay zero between calls)
         # instead of the combine kernel -- measured slower in the graphed step at every batch
@@ -245,6 +274,7 @@ class Engine:
         self.free_slots = list(range(max_batch))
         self.active: dict[int, Request] = {}
         self.waiting: list[Request] = []
+        self.prefilling: list[Request] = []  # paged prefill: admitted, prompt not complete yet (FIFO)
         self.lens = [0] * max_batch
         self._ids = itertools.count()
         self._lock = threading.Lock()
@@ -268,6 +298,9 @@ class Engine:
         self.ttft_sum = 0.0
         self.latency_sum = 0.0
         self.finished = 0
+        self.prefix_query_tokens = 0  # prompt tokens of requests admitted with the prefix cache on
+        self.prefix_hit_tokens = 0    # ... of which served from cached blocks
+        self.prefill_chunks = 0       # segments run by prefill_segments in step()
 
     # ------------------------------------------------------------------ model pieces
     def _norm_proj(self, delta, h, gamma, lin, swiglu: bool):
@@ -452,6 +485,56 @@ class Engine:
         xn = self._layers(x, attn, lora=lora)
         for s_, S, a in zip(slots, lens, aidx):
             self.lens[s_] = S
+            self.slot_adapter[s_] = a
+        last = torch.tensor([o - 1 for o in offs[1:]], device=self.device)
+        return self._logits(xn.index_select(0, last)).float()
+
+    @torch.no_grad()
+    def prefill_segments(self, slots: list[int], chunks: list[list[int]], starts: list[int],
+                         adapters=None) -> torch.Tensor:
+        """The general prefill pass: ``chunks[j]`` are the tokens at positions ``starts[j] ..`` of
+        cache slot ``slots[j]``, whose rows [0, starts[j]) are already in the cache (an earlier chunk
+        or shared prefix blocks).  The chunks' tokens are concatenated through the GEMMs like
+        ``prefill_batch``; attention is ``dops.prefill_attention_paged`` -- RoPE and the cache append
+        of the chunk, then causal attention of each chunk over its slot's rows in the block pool.
+        Returns the last-row logits of each chunk [n, V] f32.  ``adapters`` as in ``prefill_batch``."""
+        m, c = self.model, self.cfg
+        if self.kv.fp8 or self.tp is not None:
+            raise NotImplementedError("prefill_segments: bf16 KV cache, single GPU")
+        ns = [len(ch) for ch in chunks]
+        if not (len(slots) == len(chunks) == len(starts)) or any(n <= 0 for n in ns) or any(st < 0 for st in starts):
+            raise ValueError("prefill_segments: one non-empty chunk and one start >= 0 per slot")
+        if len(set(slots)) != len(slots):
+            raise ValueError("prefill_segments: one chunk per slot and pass")
+        if any(st + n >= self.max_seq for st, n in zip(starts, ns)):
+            raise ValueError(f"prompt exceeds max_seq {self.max_seq}")
+        aidx = [self._adapter_index(a) for a in adapters] if adapters is not None else [-1] * len(chunks)
+        if len(aidx) != len(chunks):
+            raise ValueError("one adapter (or None) per chunk")
+        for s_, st, n in zip(slots, starts, ns):
+            self._ensure(s_, st + n + 1)
+        t = torch.tensor([tok for ch in chunks for tok in ch], dtype=torch.long, device=self.device)
+        x = ops.embedding(t, m.tok_emb)
+        offs = [0]
+        for n in ns:
+            offs.append(offs[-1] + n)
+        plan = dops.PrefillPlan([(offs[j], ns[j], slots[j], starts[j]) for j in range(len(chunks))], offs[-1],
+                                self.device, block_table=self.kv.bt_host)
+
+        def attn(i, qkv):
+            return dops.prefill_attention_paged(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], self.kv.bt,
+                                                plan, c.n_heads, c.n_kv_heads, c.head_dim)
+
+        lora = None
+        if any(a >= 0 for a in aidx):
+            segs = ops.lora_serve.merge_segments([a for a, n in zip(aidx, ns) for _ in range(n)])
+
+            def lora(i, proj, y, xin):
+                ops.lora_delta_rows_(y, xin, None, self.lora.layers[i][proj], segments=segs)
+
+        xn = self._layers(x, attn, lora=lora)
+        for s_, st, n, a in zip(slots, starts, ns, aidx):
+            self.lens[s_] = st + n
             self.slot_adapter[s_] = a
         last = torch.tensor([o - 1 for o in offs[1:]], device=self.device)
         return self._logits(xn.index_select(0, last)).float()
@@ -724,10 +807,12 @@ class Engine:
             if name not in self.adapters:
                 raise ValueError(f"unknown LoRA adapter {name!r}")
             with self._lock:
-                busy = any(r.adapter == name for r in list(self.waiting) + list(self.active.values()))
+                busy = any(r.adapter == name
+                           for r in list(self.waiting) + self.prefilling + list(self.active.values()))
             if busy:
                 raise ValueError(f"adapter {name!r} is in use by a waiting or active request")
             self.lora.clear(self.adapters.pop(name))
+            self.kv.drop_adapter(name)  # the prefix cache's entries of this adapter
 
         return self._between_steps(do)
 
@@ -747,7 +832,8 @@ class Engine:
                 "prefill_tokens_per_s": self.prefill_tokens / self.prefill_s if self.prefill_s else 0.0,
                 "decode_tokens_per_s": self.decode_tokens / self.decode_s if self.decode_s else 0.0,
                 "decode_steps": self.steps, "kv_cache_dtype": self.kv_dtype, "kv_cache_bytes": self.kv.nbytes(),
-                "lora_adapters": sorted(self.adapters)}
+                "lora_adapters": sorted(self.adapters), "prefix_cache_query_tokens": self.prefix_query_tokens,
+                "prefix_cache_hit_tokens": self.prefix_hit_tokens, "prefill_chunks": self.prefill_chunks}
 
     def _finish(self, r: Request, reason: str):
         r.finish_reason = reason
@@ -756,7 +842,13 @@ class Engine:
         self.latency_sum += r.t_done - r.t_submit
         if r.t_first is not None:
             self.ttft_sum += r.t_first - r.t_submit
+        if r in self.prefilling:
+            self.prefilling.remove(r)
         if r.slot >= 0:
+            if self.prefix_cache:
+                # prompt and output: what multi-turn chat resends.  Only blocks below the slot's written
+                # length (a request that failed mid-prefill registers only fully written blocks)
+                self.kv.register(r.slot, r.prompt + r.output, r.adapter, upto=self.lens[r.slot])
             self.kv.release(r.slot)
             self.slot_adapter[r.slot] = -1
             self.free_slots.append(r.slot)
@@ -823,7 +915,11 @@ class Engine:
 
     def step(self) -> bool:
         """Admit + prefill waiting requests into free slots, then one decode step
-        for the running batch.  Returns False when there is nothing to do."""
+        for the running batch.  Returns False when there is nothing to do.
+        With ``prefix_cache`` / ``prefill_chunk`` on: at admission the request's prompt is matched
+        against the cached blocks under its adapter (it starts at position 256 * matched blocks and
+        reserves prompt + max_new_tokens with those blocks shared), and the prefill part is
+        ``_prefill_paged``.  Two new requests of one admission pass that share a prefix both miss."""
         with self._lock:
             admit, rejected = [], []
             while self.waiting and self.free_slots:
@@ -845,11 +941,24 @@ class Engine:
                     r.error = f"unknown LoRA adapter {r.adapter!r}"
                     rejected.append(r)
                     continue
-                if not self.kv.can_reserve(need):  # paged pool full: wait for finishing requests
+                if self.paged_prefill and not 0 < len(r.prompt) < self.max_seq:
+                    # (known before the first chunk runs, not after the last one)
+                    self.waiting.pop(0)
+                    r.error = f"prompt of {len(r.prompt)} tokens: must hold 1 .. max_seq - 1 = {self.max_seq - 1}"
+                    rejected.append(r)
+                    continue
+                shared = self.kv.match_prefix(r.prompt, r.adapter) if self.prefix_cache else []
+                if not self.kv.can_reserve(need, shared):  # paged pool full: wait for finishing requests
                     break
                 self.waiting.pop(0)
                 r.slot = self.free_slots.pop(0)
-                self.kv.reserve(r.slot, need)
+                self.kv.reserve(r.slot, need, shared=shared)
+                if self.paged_prefill:
+                    r.cached_tokens = r.prefilled = len(shared) * self.kv.block
+                    self.lens[r.slot] = r.prefilled
+                    if self.prefix_cache:
+                        self.prefix_query_tokens += len(r.prompt)
+                        self.prefix_hit_tokens += r.cached_tokens
                 admit.append(r)
         for r in rejected:
             self._finish(r, "error")
@@ -857,6 +966,10 @@ class Engine:
             admit = self._sync_admit(admit)
         for r in admit:
             self._admit_state(r)
+        if self.paged_prefill:
+            self.prefilling.extend(admit)
+            self._prefill_paged()
+            admit = []  # (their prefill ran, or goes on in later steps)
         # admitted prompts are prefilled together, in groups of at most
         # prefill_tokens tokens (bounds the activation memory of one pass)
         groups, cur, ntok = [], [], 0
@@ -887,7 +1000,7 @@ class Engine:
                     r.error = str(e)
                     self._finish(r, "error")
         if not self.active:
-            return bool(admit)
+            return bool(admit) or bool(self.prefilling)
         slots = sorted(self.active)
         reqs = [self.active[s] for s in slots]
         t0 = time.perf_counter()
@@ -900,6 +1013,65 @@ class Engine:
         for r, t in zip(reqs, nxt):
             self._accept(r, int(t))
         return True
+
+    def _prefill_paged(self) -> None:
+        """The prefill part of a step with ``prefix_cache`` or ``prefill_chunk`` on.  Requests still
+        prefilling go first, FIFO, then the new admissions.  ``prefill_chunk`` = N: ONE pass of at
+        most N tokens, the last segment cut to fit; unset: the uncached remainders, grouped by
+        ``prefill_tokens`` like ``prefill_batch``'s groups.  A request whose prompt completes in a
+        pass is sampled and joins ``active``; its prompt's full blocks are registered at once, so
+        later admissions share them while it still runs."""
+        passes, cur, ntok = [], [], 0
+        if self.prefill_chunk is not None:
+            left = self.prefill_chunk
+            for r in self.prefilling:
+                n = min(len(r.prompt) - r.prefilled, left)
+                if n <= 0:
+                    break
+                cur.append((r, n))
+                left -= n
+        else:
+            for r in self.prefilling:
+                n = len(r.prompt) - r.prefilled
+                if cur and ntok + n > self.prefill_budget:
+                    passes.append(cur)
+                    cur, ntok = [], 0
+                cur.append((r, n))
+                ntok += n
+        if cur:
+            passes.append(cur)
+        for grp in passes:
+            reqs = [r for r, _ in grp]
+            try:
+                t0 = time.perf_counter()
+                logits = self.prefill_segments([r.slot for r in reqs], [r.prompt[r.prefilled:r.prefilled + n] for r, n in grp],
+                                               [r.prefilled for r in reqs],
+                                               [r.adapter for r in reqs] if self.lora is not None else None)
+                self.prefill_chunks += len(grp)
+                done = []
+                for j, (r, n) in enumerate(grp):
+                    r.prefilled += n
+                    self.prefill_tokens += n
+                    if r.prefilled == len(r.prompt):
+                        done.append(j)
+                if done:
+                    fin = [reqs[j] for j in done]
+                    for r in fin:
+                        self.prefilling.remove(r)
+                        self.active[r.slot] = r
+                        if self.prefix_cache:
+                            self.kv.register(r.slot, r.prompt, r.adapter, upto=len(r.prompt))
+                    rows = logits if len(done) == len(grp) else logits[torch.tensor(done, device=logits.device)]
+                    toks = self._sample(rows, fin, first=True)
+                    for r, tok in zip(fin, toks):
+                        self._accept(r, tok)
+                self.prefill_s += time.perf_counter() - t0
+            except Exception as e:  # noqa: BLE001
+                log.exception("prefill failed")
+                for r in reqs:
+                    self.active.pop(r.slot, None)
+                    r.error = str(e)
+                    self._finish(r, "error")
 
     def _admit_state(self, r: Request) -> None:
         """Device state of a request that uses a penalty or a logit_bias: its slot's rows of
@@ -1065,7 +1237,8 @@ class Engine:
             sync = getattr(self, "tp_sync", False)
             while True:  # leaves only through the stop branch, which always tells the followers
                 with self._cv:
-                    while not self._stop and not self.waiting and not self.active and not self._tasks:
+                    while (not self._stop and not self.waiting and not self.active and not self.prefilling
+                           and not self._tasks):
                         self._cv.wait(timeout=0.5)
                         if sync:  # idle heartbeat: followers wait inside a broadcast
                             break

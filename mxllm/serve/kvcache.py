@@ -27,10 +27,24 @@ uint8 code pools of the same shape and ``k_scale`` / ``v_scale`` f32 pools ``[bl
 hold one power-of-two scale per (token, KV head) row: 132 bytes per row instead of 256.  ``write``
 quantises (HIP ``kv8_quant_rows``; CPU: the codec), ``gather`` returns the dequantised bf16 rows,
 and block accounting is the same.
+
+``prefix_cache=True`` (paged mode only): blocks are reference-counted and FULL blocks can be shared
+between sequences.  An index maps ``(adapter key, parent entry id, tuple of the block's token
+ids)`` to ``(entry id, block)``: a block is found only through the chain of its predecessors, so it
+holds the K/V of exactly that token prefix under that adapter.  Entry ids count up and are never
+reused -- an evicted and re-used block can never be reached through a stale child -- and the token
+tuple itself is the dict key, not its hash, so a hash collision cannot serve the wrong K/V.
+``match_prefix`` finds the longest cached chain, ``reserve(..., shared=blocks)`` puts it first in the
+slot's table row, ``register`` enters a slot's full blocks, ``release`` lowers the counts:
+unreferenced indexed blocks wait in an LRU list (last block of a chain first, so a chain is evicted
+from its tail) and are evicted only when the free list is empty.  A shared block is full and never
+written: a sequence writes only positions at or beyond its cached length, which lie in its own blocks.
 """
 from __future__ import annotations
 
+import itertools
 import math
+from collections import OrderedDict
 
 import torch
 
@@ -41,7 +55,9 @@ KV_DTYPES = ("bf16", "fp8")
 class KVCache:
     def __init__(self, n_layers: int, n_kv_heads: int, head_dim: int, dtype, device, n_slots: int, max_seq: int,
                  pool_tokens: int | None = None, block: int = BLOCK, scratch_slot: int | None = None,
-                 kv_dtype: str = "bf16"):
+                 kv_dtype: str = "bf16", prefix_cache: bool = False):
+        if prefix_cache and pool_tokens is None:
+            raise ValueError("prefix_cache needs the paged KV cache (pool_tokens)")
         if block % 256:
             raise ValueError("KV block size must be a multiple of 256 tokens (the decode split)")
         if kv_dtype not in KV_DTYPES:
@@ -85,6 +101,13 @@ class KVCache:
             self.owned[scratch_slot] = [n_blocks - 1]
             self.bt_host[scratch_slot, :] = n_blocks - 1
         self.bt = self.bt_host.to(device)
+        # prefix cache: reference counts, the index and the LRU list of unreferenced indexed blocks
+        self.prefix_cache = bool(prefix_cache)
+        self.ref = [0] * n_blocks
+        self.index: dict[tuple, tuple[int, int]] = {}      # (adapter, parent entry, tokens) -> (entry, block)
+        self.block_key: dict[int, tuple] = {}              # indexed block -> its index key
+        self.lru: OrderedDict[int, None] = OrderedDict()   # unreferenced indexed blocks, evicted from the front
+        self._entry_ids = itertools.count(1)               # 0: the root (no parent)
 
     # ------------------------------------------------------------------ accounting
     def blocks_for(self, tokens: int) -> int:
@@ -94,22 +117,48 @@ class KVCache:
     def free_blocks(self) -> int:
         return len(self.free) if self.paged else 0
 
-    def can_reserve(self, tokens: int) -> bool:
-        return not self.paged or self.blocks_for(tokens) <= len(self.free)
+    @property
+    def evictable_blocks(self) -> int:
+        return len(self.lru)
+
+    def can_reserve(self, tokens: int, shared=()) -> bool:
+        """``shared``: cached blocks the reservation would take from ``match_prefix`` (they are not
+        taken from the free list, and those waiting in the LRU list are not evictable for it)."""
+        if not self.paged:
+            return True
+        have = len(self.free) + len(self.lru) - sum(1 for b in shared if b in self.lru)
+        return self.blocks_for(tokens) - len(shared) <= have
 
     def fits_at_all(self, tokens: int) -> bool:
         return not self.paged or self.blocks_for(tokens) <= self.n_blocks - (1 if self.scratch_slot is not None else 0)
 
-    def reserve(self, slot: int, tokens: int) -> None:
+    def reserve(self, slot: int, tokens: int, shared=()) -> None:
         """Give ``slot`` the blocks for positions [0, tokens) (paged mode; a no-op
-        in static mode, where every slot owns max_seq positions)."""
+        in static mode, where every slot owns max_seq positions).  ``shared`` (prefix cache): the
+        cached blocks of ``match_prefix`` come first in the table row, their counts raised; the rest
+        comes from the free list and, when that is empty, from the least-recently-used unreferenced
+        cached blocks, which are evicted."""
         if not self.paged:
             return
         self.release(slot)
         n = self.blocks_for(tokens)
-        if n > len(self.free):
-            raise RuntimeError(f"KV pool exhausted: need {n} blocks, {len(self.free)} free")
-        blocks, self.free = self.free[:n], self.free[n:]
+        shared = list(shared)
+        if shared and not self.prefix_cache:
+            raise ValueError("shared blocks need prefix_cache=True")
+        if len(shared) > n:
+            raise ValueError(f"{len(shared)} shared blocks for a reservation of {n}")
+        if not self.can_reserve(tokens, shared):
+            raise RuntimeError(f"KV pool exhausted: need {n - len(shared)} blocks, {len(self.free)} free, "
+                               f"{len(self.lru)} evictable")
+        for b in shared:  # referenced first: a block in use is never evicted
+            self.ref[b] += 1
+            self.lru.pop(b, None)
+        own = n - len(shared)
+        while len(self.free) < own:
+            self._evict()
+        blocks, self.free = shared + self.free[:own], self.free[own:]
+        for b in blocks[len(shared):]:
+            self.ref[b] = 1
         self.owned[slot] = blocks
         row = torch.zeros(self.maxb, dtype=torch.int32)
         row[:n] = torch.tensor(blocks, dtype=torch.int32)
@@ -124,8 +173,78 @@ class KVCache:
         return min(len(self.owned.get(slot, ())) * self.block, self.max_seq)
 
     def release(self, slot: int) -> None:
-        if self.paged and slot in self.owned and slot != self.scratch_slot:
-            self.free.extend(self.owned.pop(slot))
+        if not (self.paged and slot in self.owned and slot != self.scratch_slot):
+            return
+        blocks = self.owned.pop(slot)
+        if not self.prefix_cache:
+            self.free.extend(blocks)
+            return
+        for b in reversed(blocks):  # the last block of a chain enters the LRU list first: evicted first
+            self.ref[b] -= 1
+            if self.ref[b] > 0:
+                continue
+            if b in self.block_key:
+                self.lru[b] = None
+                self.lru.move_to_end(b)
+            else:
+                self.free.append(b)
+
+    # ------------------------------------------------------------------ prefix cache
+    def _evict(self) -> int:
+        """Drop the least-recently-used unreferenced cached block from the index; it joins the free list."""
+        b, _ = self.lru.popitem(last=False)
+        del self.index[self.block_key.pop(b)]
+        self.free.append(b)
+        return b
+
+    def match_prefix(self, tokens, adapter=None) -> list[int]:
+        """The longest chain of cached full blocks that holds a prefix of ``tokens`` under ``adapter``
+        (any hashable key; None: the base model), at most ``(len(tokens) - 1) // block`` blocks so
+        that at least one token is always computed."""
+        if not self.prefix_cache:
+            return []
+        out, parent = [], 0
+        for j in range((len(tokens) - 1) // self.block):
+            hit = self.index.get((adapter, parent, tuple(tokens[j * self.block:(j + 1) * self.block])))
+            if hit is None:
+                break
+            parent = hit[0]
+            out.append(hit[1])
+        return out
+
+    def register(self, slot: int, tokens, adapter=None, upto: int | None = None) -> int:
+        """Enter the full blocks of ``slot`` that lie below ``upto`` written positions (default: all of
+        ``tokens``) into the index; ``tokens`` are the ids at the slot's positions.  A key that is
+        already present keeps its block: the slot keeps its own copy, unindexed, and the chain goes on
+        under the indexed entry.  Returns the number of blocks newly entered."""
+        if not self.prefix_cache or slot not in self.owned or slot == self.scratch_slot:
+            return 0
+        upto = len(tokens) if upto is None else min(upto, len(tokens))
+        blocks, parent, new = self.owned[slot], 0, 0
+        for j in range(min(upto // self.block, len(blocks))):
+            key = (adapter, parent, tuple(tokens[j * self.block:(j + 1) * self.block]))
+            hit = self.index.get(key)
+            if hit is None:
+                if blocks[j] in self.block_key:  # already indexed under another chain: leave it there
+                    break
+                hit = (next(self._entry_ids), blocks[j])
+                self.index[key] = hit
+                self.block_key[blocks[j]] = key
+                new += 1
+            parent = hit[0]
+        return new
+
+    def drop_adapter(self, adapter) -> int:
+        """Remove every index entry of ``adapter``: unreferenced blocks join the free list, blocks
+        still in use become ordinary owned blocks.  Returns the number of entries removed."""
+        keys = [k for k in self.index if k[0] == adapter]
+        for k in keys:
+            _, b = self.index.pop(k)
+            del self.block_key[b]
+            if b in self.lru:
+                del self.lru[b]
+                self.free.append(b)
+        return len(keys)
 
     # ------------------------------------------------------------------ data
     def write(self, layer: int, slot: int, k: torch.Tensor, v: torch.Tensor) -> None:

@@ -133,8 +133,11 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
         return out
 
     def usage(r):
-        return {"prompt_tokens": len(r.prompt), "completion_tokens": len(r.output),
-                "total_tokens": len(r.prompt) + len(r.output)}
+        u = {"prompt_tokens": len(r.prompt), "completion_tokens": len(r.output),
+             "total_tokens": len(r.prompt) + len(r.output)}
+        if getattr(engine, "prefix_cache", False):  # OpenAI's field: prompt tokens served from the prefix cache
+            u["prompt_tokens_details"] = {"cached_tokens": r.cached_tokens}
+        return u
 
     @app.get("/health")
     async def health():
@@ -157,6 +160,9 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
                  f"mxllm_request_latency_seconds_sum {engine.latency_sum:.6f}",
                  f"mxllm_request_latency_seconds_count {engine.finished}",
                  f"mxllm_prefill_tokens_total {engine.prefill_tokens}",
+                 f"mxllm_prefix_cache_query_tokens_total {getattr(engine, 'prefix_query_tokens', 0)}",
+                 f"mxllm_prefix_cache_hit_tokens_total {getattr(engine, 'prefix_hit_tokens', 0)}",
+                 f"mxllm_prefill_chunks_total {getattr(engine, 'prefill_chunks', 0)}",
                  f"mxllm_prefill_seconds_total {engine.prefill_s:.6f}",
                  f"mxllm_decode_tokens_total {engine.decode_tokens}",
                  f"mxllm_decode_seconds_total {engine.decode_s:.6f}",
@@ -297,13 +303,16 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
 def build_default(model: str = "tiny", device: str | None = None, max_batch: int = 8, max_seq: int = 2048,
                   checkpoint: str | None = None, tokenizer_path: str | None = None, seed: int = 0,
                   weights: str = "bf16", tp_group=None, kv_cache: str | None = None, adapters: dict | None = None,
-                  max_loras: int | None = None, max_lora_rank: int = 16):
+                  max_loras: int | None = None, max_lora_rank: int = 16, prefix_cache: bool | None = None,
+                  prefill_chunk: int | None = None, kv_pool_tokens: int | None = None):
     """Engine + tokenizer.  ``tp_group``: this rank serves its tensor-parallel
     shard (mxllm/parallel/tensor.py) of the model; the full model is built (or
     loaded) on the rank's GPU, sliced and freed.  ``kv_cache``: "bf16" / "fp8" KV cache
     (None: env MXLLM_KV_CACHE, default bf16; ``Engine(kv_dtype=...)``).  ``adapters``: {name: PEFT
     LoRA directory} served beside the base model (``max_loras`` table slots, default one per adapter,
-    each of rank <= ``max_lora_rank``); a request whose ``model`` is such a name runs on that adapter."""
+    each of rank <= ``max_lora_rank``); a request whose ``model`` is such a name runs on that adapter.
+    ``prefix_cache`` / ``prefill_chunk`` / ``kv_pool_tokens``: the engine's options of the same names
+    (None: their env variables)."""
     from ..data.tokenizer import get_tokenizer
     from ..models import build_model, tokenizer_path_for
 
@@ -333,7 +342,8 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
     tok = get_tokenizer(cfg.vocab_size, tokenizer_path, cfg.bos_id, cfg.eos_id)
     eng = Engine(m, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id, getattr(tok, "eos_id", cfg.eos_id)),
                  tp_group=tp_group, kv_dtype=kv_cache,
-                 max_adapters=max(max_loras or 0, len(adapters or {})), max_lora_rank=max_lora_rank)
+                 max_adapters=max(max_loras or 0, len(adapters or {})), max_lora_rank=max_lora_rank,
+                 prefix_cache=prefix_cache, prefill_chunk=prefill_chunk, kv_pool_tokens=kv_pool_tokens)
     for name, path in (adapters or {}).items():
         eng.load_adapter(name, path)
     return eng, tok
@@ -376,6 +386,14 @@ def parse_args(argv=None):
     ap.add_argument("--max-loras", type=int, default=None, help="adapter table slots (default: one per --lora)")
     ap.add_argument("--max-lora-rank", type=int, default=16, choices=[8, 16, 32, 64],
                     help="rank of the adapter tables; adapters of a lower rank are zero-padded")
+    ap.add_argument("--kv-pool-tokens", type=int, default=None,
+                    help="paged KV cache: a pool of that many tokens shared by all slots (env MXLLM_KV_POOL_TOKENS)")
+    ap.add_argument("--prefix-cache", action="store_true", default=None,
+                    help="share the KV blocks of common prompt prefixes between requests (needs the paged KV "
+                         "cache: --kv-pool-tokens; bf16 KV cache, --tp 1; env MXLLM_PREFIX_CACHE=1)")
+    ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
+                    help="prefill at most N prompt tokens per engine step, so a long prompt does not stall the "
+                         "streaming requests (bf16 KV cache, --tp 1; env MXLLM_PREFILL_CHUNK)")
     return ap.parse_args(argv)
 
 
@@ -394,7 +412,8 @@ def main(argv=None):
         group = dist.group.WORLD
     eng, tok = build_default(a.model, None, a.max_batch, a.max_seq, a.checkpoint, a.tokenizer, weights=a.weights,
                              tp_group=group, kv_cache=a.kv_cache, adapters=parse_lora_modules(a.lora),
-                             max_loras=a.max_loras, max_lora_rank=a.max_lora_rank)
+                             max_loras=a.max_loras, max_lora_rank=a.max_lora_rank, prefix_cache=a.prefix_cache,
+                             prefill_chunk=a.prefill_chunk, kv_pool_tokens=a.kv_pool_tokens)
     if group is not None:
         eng.enable_tp_sync()
         if env.rank != 0:
