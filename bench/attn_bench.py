@@ -43,8 +43,6 @@ def main():
     if not lite:
         res["bwd_atomic_ms"] = timeit(lambda: ops.attn_bwd(do, q, k, v, o, lse, True, sc, 1))
         res["bwd_partials_ms"] = timeit(lambda: ops.attn_bwd(do, q, k, v, o, lse, True, sc, 2))
-        res["bwd_noatomic_ms"] = timeit(lambda: ops.attn_bwd_ablate(do, q, k, v, o, lse, -1, sc))
-        res["bwd_noatomic_TF"] = 2.5 * fl / res["bwd_noatomic_ms"] / 1e9
     cs = torch.rand(S, D // 2, device=dev)
     res["bwd_rope_ms"] = timeit(lambda: ops.attn_bwd_rope(do, q, k, v, o, lse, True, sc, cs, cs, 0))  # into d(qkv)
     res["fwd_TF"] = fl / res["fwd_ms"] / 1e9

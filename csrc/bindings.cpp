@@ -703,105 +703,124 @@ at::Tensor rope_merge_bwd(const at::Tensor& dq, const at::Tensor& dkp, const at:
 }
 
 // ---------------------------------------------------------------- attention
+// Operand checks of attn_fwd, attn_bwd and attn_bwd_rope: all run before anything is allocated or written;
+// the shape rules themselves are mx::af_takes / mx::ab_takes (kernels/attn_args.h).
+typedef c10::optional<at::Tensor> OptTensor;
+static void attn_operand(const char* op, const char* name, const at::Tensor& t, at::Device dev, at::ScalarType dt) {
+  MX_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == dt && t.is_contiguous(), op, ": ", name,
+           " must be a contiguous ", c10::toString(dt), " GPU tensor on q's device");
+}
+// rc of a launcher (or of a check) that was handed L: -1 is a refusal (nothing was launched), > 0 a HIP error
+static void attn_launched(const char* op, int rc, const mx::AbLaunch& L) {
+  MX_CHECK(rc != -1, op, ": the kernels do not take this call (mx::af_takes / mx::ab_takes, kernels/attn_args.h): B ",
+           L.B, ", Hq ", L.Hq, ", Hkv ", L.Hkv, ", S ", L.S, ", Sk ", L.Sk, ", D ", L.D, ", causal ", L.causal,
+           ", dq_mode ", L.dq_mode, ", row strides o ", L.ldo, ", dqkv ", L.ldq);
+  TORCH_CHECK(rc == 0, "mxllm kernel launch failed (", op, ") rc=", rc, " ", hipGetErrorString((hipError_t)rc));
+}
+// The description of a call from its tensors: q [B,Hq,S,D], k / v [B,Hkv,Sk,D] on one device; for the
+// backward (dout given) also o, dout, lse, the RoPE tables, preallocated outputs, L.hpw and the shape rules.
+static mx::AbLaunch attn_fill(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                              bool causal, int64_t dq_mode = 3, const at::Tensor* o = nullptr,
+                              const at::Tensor* dout = nullptr, const at::Tensor* lse = nullptr,
+                              const at::Tensor* cos = nullptr, const at::Tensor* sin = nullptr,
+                              const OptTensor& dq_out = c10::nullopt, const OptTensor& dk_out = c10::nullopt,
+                              const OptTensor& dv_out = c10::nullopt) {
+  MX_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, op, ": q [B,Hq,S,D], k/v [B,Hkv,Sk,D]");
+  const at::Device dev = q.device();
+  for (auto [n, t] : {std::pair{"q", &q}, {"k", &k}, {"v", &v}}) attn_operand(op, n, *t, dev, at::kBFloat16);
+  mx::AbLaunch L{};
+  L.B = q.size(0), L.Hq = q.size(1), L.S = q.size(2), L.D = q.size(3), L.Hkv = k.size(1), L.Sk = k.size(2);
+  MX_CHECK(k.size(0) == L.B && k.size(3) == L.D && v.sizes() == k.sizes(), op, ": k ", k.sizes(), " and v ", v.sizes(),
+           " must be [B,Hkv,Sk,D] for q ", q.sizes());
+  L.q = q.data_ptr(), L.k = k.data_ptr(), L.v = v.data_ptr(), L.q_bf16 = L.kv_bf16 = 1;
+  L.causal = causal ? 1 : 0, L.dq_mode = (int)dq_mode, L.ldo = L.Hq * L.D, L.hpw = 1;
+  if (!dout) return L;
+  MX_CHECK(dq_mode >= 1 && dq_mode <= 3, op, ": dq_mode must be 1, 2 or 3");
+  attn_operand(op, "dout", *dout, dev, at::kBFloat16);
+  attn_operand(op, "lse", *lse, dev, at::kFloat);
+  MX_CHECK(dout->numel() == q.numel() && o->numel() == dout->numel(), op, ": dout/o shape");
+  MX_CHECK(lse->numel() == L.B * L.Hq * L.S, op, ": lse must be [B,Hq,S], got ", lse->sizes());
+  if (o->is_contiguous()) {
+    attn_operand(op, "o", *o, dev, at::kBFloat16);
+  } else {  // token rows with a row stride (the padded attention output)
+    MX_CHECK(o->is_cuda() && o->device() == dev && o->scalar_type() == at::kBFloat16 && o->dim() == 3 &&
+                 o->stride(2) == 1 && o->size(2) == L.Hq * L.D && o->stride(0) == L.S * o->stride(1) &&
+                 o->stride(1) % 8 == 0, op, ": o must be [B, S, Hq*D] with unit inner stride");
+    L.ldo = o->stride(1);
+  }
+  L.o = o->data_ptr(), L.dout = dout->data_ptr(), L.lse = lse->data_ptr();
+  L.o_bf16 = L.dout_bf16 = L.lse_f32 = L.out_f32 = 1;
+  if (cos) {  // the backward that writes d(qkv) itself
+    MX_CHECK(mx::ab_takes_rope(dq_mode, L.D, L.S, L.Sk), op, ": D = 128 self-attention in the split mode");
+    for (auto [n, t] : {std::pair{"cos", cos}, {"sin", sin}}) attn_operand(op, n, *t, dev, at::kFloat);
+    MX_CHECK(L.D >= 2 && cos->numel() >= L.S * (L.D / 2) && sin->numel() >= L.S * (L.D / 2), op,
+             ": cos / sin: [>= S, D/2] contiguous f32");
+    L.cos = cos->data_ptr(), L.sin = sin->data_ptr();
+    L.cos_rows = std::min(cos->numel(), sin->numel()) / (L.D / 2);
+  }
+  const int64_t P = mx_attn_bwd_partial_heads(L);  // dK / dV partials [B, P, Sk, D], a KV head's consecutive
+  if (dq_out.has_value() || dk_out.has_value() || dv_out.has_value()) {
+    MX_CHECK(dq_out.has_value() && dk_out.has_value() && dv_out.has_value() && dq_mode == 3, op,
+             ": preallocated outputs need all three and the split mode");
+    for (auto [n, t] : {std::pair{"dq_out", &*dq_out}, {"dk_out", &*dk_out}, {"dv_out", &*dv_out}})
+      attn_operand(op, n, *t, dev, at::kFloat);
+    MX_CHECK(dq_out->numel() == q.numel() && dk_out->numel() == L.B * P * L.Sk * L.D &&
+                 dv_out->numel() == L.B * P * L.Sk * L.D, op, ": output sizes");
+  }
+  attn_launched(op, mx::ab_shape_takes(L) ? 0 : -1, L);
+  return L;
+}
+
 // out_pad > 0: o [B, S, Hq*D] is a view into [B, S, Hq*D + out_pad] (row stride Hq*D + out_pad)
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                             bool causal, double scale, int64_t out_pad) {
-  check_bf16(q, "q");
-  check_bf16(k, "k");
-  check_bf16(v, "v");
-  MX_CHECK(q.dim() == 4 && k.dim() == 4 && v.sizes() == k.sizes(), "q [B,Hq,S,D], k/v [B,Hkv,Sk,D]");
-  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), D = q.size(3);
-  const int64_t Hkv = k.size(1), Sk = k.size(2);
-  MX_CHECK(k.size(0) == B && k.size(3) == D && Hq % Hkv == 0, "attention shape mismatch");
-  DevGuard g(q.device());
+  mx::AbLaunch S = attn_fill("attn_fwd", q, k, v, causal);
   MX_CHECK(out_pad >= 0 && out_pad % 8 == 0, "out_pad must be a non-negative multiple of 8");
-  auto o = out_pad > 0 ? at::empty({B, S, Hq * D + out_pad}, q.options()).narrow(2, 0, Hq * D)
-                       : at::empty({B, S, Hq * D}, q.options());
-  auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  MX_OK(mx_attn_fwd(bf(q), bf(k), bf(v), bfm(o), lse.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv, (int)S, (int)Sk,
-                    (int)D, causal ? 1 : 0, (float)scale, (int)(Hq * D + out_pad), cur_stream()));
+  S.ldo += out_pad;
+  DevGuard g(q.device());
+  auto o = at::empty({S.B, S.S, S.ldo}, q.options()).narrow(2, 0, S.Hq * S.D);  // (the whole of it without out_pad)
+  auto lse = at::empty({S.B, S.Hq, S.S}, q.options().dtype(at::kFloat));
+  mx::AfLaunch L{S.q, S.k, S.v, o.data_ptr(), lse.data_ptr(), 1, 1, 1, 1, S.B, S.Hq, S.Hkv, S.S, S.Sk, S.D, S.ldo};
+  L.causal = S.causal;
+  attn_launched("attn_fwd", mx_attn_fwd(L, (float)scale, cur_stream()), S);
   return {o, lse};
 }
 
-// dq_mode: 1 = f32 atomics, 2 = deterministic per-key-block partials + ordered reduce,
-// 3 = split (dS^T to HBM + separate dQ kernel; default, deterministic)
-// outs (optional, split mode only): preallocated f32 dq [B, Hq, S, D] and dK / dV partials
-// [B, P, Sk, D] to write into (e.g. head-range views of larger tensors: the chunked long-context
-// backward, mxllm/ops/attention.py) instead of fresh tensors.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd_impl(const at::Tensor& dout, const at::Tensor& q,
-                                                             const at::Tensor& k, const at::Tensor& v,
-                                                             const at::Tensor& o, const at::Tensor& lse, int causal,
-                                                             double scale, int64_t dq_mode,
-                                                             const c10::optional<at::Tensor>& dq_out = c10::nullopt,
-                                                             const c10::optional<at::Tensor>& dk_out = c10::nullopt,
-                                                             const c10::optional<at::Tensor>& dv_out = c10::nullopt,
-                                                             uint16_t* dqkv = nullptr, int64_t ldq = 0,
-                                                             const float* cosb = nullptr, const float* sinb = nullptr) {
-  check_bf16(dout, "dout");
-  check_f32(lse, "lse");
-  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), D = q.size(3);
-  const int64_t Hkv = k.size(1), Sk = k.size(2);
-  MX_CHECK(dout.numel() == B * S * Hq * D && o.numel() == dout.numel(), "dout/o shape");
-  MX_CHECK(dq_mode >= 1 && dq_mode <= 3, "dq_mode must be 1, 2 or 3");
-  // o: contiguous, or token rows with a row stride (the padded attention output)
-  int64_t ldo = Hq * D;
-  if (!o.is_contiguous()) {
-    MX_CHECK(o.is_cuda() && o.scalar_type() == at::kBFloat16 && o.dim() == 3 && o.stride(2) == 1 &&
-                 o.size(2) == Hq * D && o.stride(0) == S * o.stride(1) && o.stride(1) % 8 == 0,
-             "o must be [B, S, Hq*D] with unit inner stride");
-    ldo = o.stride(1);
-  } else {
-    check_bf16(o, "o");
-  }
+// dq_mode: mx::AbLaunch.  dq_out / dk_out / dv_out (optional, split mode only): preallocated f32 dq [B, Hq, S, D]
+// and dK / dV partials [B, P, Sk, D] to write into (head-range views of larger tensors: the chunked long-context
+// backward, mxllm/ops/attention.py).  dqkv (attn_bwd_rope): d(qkv) rows whose q columns the dQ kernel writes.
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd_impl(
+    const char* op, const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& o, const at::Tensor& lse, bool causal, double scale, int64_t dq_mode, const OptTensor& dq_out,
+    const OptTensor& dk_out, const OptTensor& dv_out, at::Tensor* dqkv = nullptr, int64_t dqkv_pad = 0,
+    const at::Tensor* cos = nullptr, const at::Tensor* sin = nullptr) {
+  mx::AbLaunch L = attn_fill(op, q, k, v, causal, dq_mode, &o, &dout, &lse, cos, sin, dq_out, dk_out, dv_out);
   DevGuard g(q.device());
-  const int64_t S_pad = (S + 63) / 64 * 64;
-  const int64_t nkb = (Sk + 127) / 128;
-  // dK / dV partials: [B, P, Sk, D] f32, P partial heads (Hq, or fewer when a workgroup of the
-  // 8-wave kernel sums several q-heads of a KV group); a KV head's partials are consecutive
-  const int64_t P = (causal >= 0 && dq_mode == 3)
-                        ? mx_attn_bwd_partial_heads((int)B, (int)Hq, (int)Hkv, (int)S, (int)Sk, (int)D, (int)dq_mode)
-                        : Hq;
-  const bool outs = dq_out.has_value() || dk_out.has_value() || dv_out.has_value();
-  if (outs) {
-    MX_CHECK(dq_out.has_value() && dk_out.has_value() && dv_out.has_value() && dq_mode == 3 && causal >= 0,
-             "attn_bwd: preallocated outputs need all three and the split mode");
-    check_f32(*dq_out, "dq_out");
-    check_f32(*dk_out, "dk_out");
-    check_f32(*dv_out, "dv_out");
-    MX_CHECK(dq_out->numel() == B * Hq * S * D && dk_out->numel() == B * P * Sk * D &&
-                 dv_out->numel() == B * P * Sk * D, "attn_bwd: output sizes");
-  }
-  auto dkp = outs ? *dk_out : at::empty({B, P, Sk, D}, q.options().dtype(at::kFloat));
-  auto dvp = outs ? *dv_out : at::empty({B, P, Sk, D}, q.options().dtype(at::kFloat));
-  auto delta = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  if (causal >= 0 && dq_mode != 1) {
-    at::Tensor work = dq_mode == 2 ? at::empty({nkb, B, Hq, S_pad, D}, q.options().dtype(at::kFloat))
-                                   : at::empty({B * Hq, nkb * 128, S_pad}, q.options());
-    // dqkv: the dQ kernel writes d(q) into it; no fp32 dQ at all
-    auto dq = outs ? *dq_out
-                   : at::empty({dqkv ? 0 : B, Hq, S, D}, q.options().dtype(at::kFloat));
-    MX_OK(mx_attn_bwd(bf(q), bf(k), bf(v), bf(o), bf(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
-                      dq.data_ptr<float>(), dkp.data_ptr<float>(), dvp.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv,
-                      (int)S, (int)Sk, (int)D, causal, (float)scale, (int)dq_mode, work.data_ptr(), ldo,
-                      cur_stream(), dqkv, ldq, cosb, sinb));
-    return {dq, dkp, dvp};
-  }
-  auto dq_pad = at::zeros({B, Hq, S_pad, D}, q.options().dtype(at::kFloat));
-  MX_OK(mx_attn_bwd(bf(q), bf(k), bf(v), bf(o), bf(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
-                    dq_pad.data_ptr<float>(), dkp.data_ptr<float>(), dvp.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv,
-                    (int)S, (int)Sk, (int)D, causal, (float)scale, 1, nullptr, ldo, cur_stream(), nullptr, 0, nullptr,
-                    nullptr));
-  auto dq = S_pad == S ? dq_pad : dq_pad.narrow(2, 0, S).contiguous();
+  const auto f32 = q.options().dtype(at::kFloat);
+  const bool outs = dq_out.has_value();
+  const int64_t P = L.Hq / L.hpw, S_pad = mx::ab_s_pad(L.S);  // P partial heads: mx::ab_hpw
+  auto dkp = outs ? *dk_out : at::empty({L.B, P, L.Sk, L.D}, f32);
+  auto dvp = outs ? *dv_out : at::empty({L.B, P, L.Sk, L.D}, f32);
+  auto delta = at::empty({L.B, L.Hq, L.S}, f32);
+  auto work = at::empty({mx::ab_work_bytes(L)}, q.options().dtype(at::kByte));
+  // mode 1: a zeroed dQ padded to whole q tiles (the tail tile's atomics need no guard)
+  auto dq = outs ? *dq_out
+                 : (dq_mode == 1 ? at::zeros({L.B, L.Hq, S_pad, L.D}, f32)
+                                 : at::empty({dqkv ? 0 : L.B, L.Hq, L.S, L.D}, f32));
+  L.delta = delta.data_ptr(), L.dq = dq.data_ptr(), L.dkp = dkp.data_ptr(), L.dvp = dvp.data_ptr();
+  if (dq_mode != 1) L.work = work.data_ptr();
+  if (dqkv) *dqkv = empty_rows(L.B * L.S, (L.Hq + 2 * L.Hkv) * L.D, dqkv_pad, q.options());
+  if (dqkv) L.dqkv = dqkv->data_ptr(), L.ldq = dqkv->stride(0), L.dqkv_bf16 = 1;
+  attn_launched(op, mx_attn_bwd(L, (float)scale, cur_stream()), L);
+  if (dq_mode == 1 && S_pad != L.S) dq = dq.narrow(2, 0, L.S).contiguous();
   return {dq, dkp, dvp};
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
-                                                        const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
-                                                        const at::Tensor& lse, bool causal, double scale,
-                                                        int64_t dq_mode, const c10::optional<at::Tensor>& dq_out,
-                                                        const c10::optional<at::Tensor>& dk_out,
-                                                        const c10::optional<at::Tensor>& dv_out) {
-  return attn_bwd_impl(dout, q, k, v, o, lse, causal ? 1 : 0, scale, dq_mode, dq_out, dk_out, dv_out);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+    const at::Tensor& lse, bool causal, double scale, int64_t dq_mode, const OptTensor& dq_out, const OptTensor& dk_out,
+    const OptTensor& dv_out) {
+  return attn_bwd_impl("attn_bwd", dout, q, k, v, o, lse, causal, scale, dq_mode, dq_out, dk_out, dv_out);
 }
 
 // The attention backward straight into d(qkv) [B*S, (Hq+2Hkv)*D (+out_pad)] bf16 (D = 128, split mode):
@@ -810,33 +829,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd(const at::Tensor& dout, 
 at::Tensor attn_bwd_rope(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                          const at::Tensor& o, const at::Tensor& lse, bool causal, double scale, const at::Tensor& cos,
                          const at::Tensor& sin, int64_t out_pad) {
-  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), D = q.size(3);
-  const int64_t Hkv = k.size(1), Sk = k.size(2);
-  MX_CHECK(D == 128 && Sk == S, "attn_bwd_rope: D = 128 self-attention");
-  check_f32(cos, "cos");
-  check_f32(sin, "sin");
-  MX_CHECK(cos.is_contiguous() && sin.is_contiguous() && cos.numel() >= S * (D / 2) && sin.numel() >= S * (D / 2),
-           "cos / sin: [>= S, D/2] contiguous f32");
   MX_CHECK(out_pad >= 0 && out_pad % 8 == 0, "out_pad must be a non-negative multiple of 8");
+  at::Tensor dqkv;
+  auto [dq, dkp, dvp] = attn_bwd_impl("attn_bwd_rope", dout, q, k, v, o, lse, causal, scale, 3, c10::nullopt,
+                                      c10::nullopt, c10::nullopt, &dqkv, out_pad, &cos, &sin);
   DevGuard g(q.device());
-  const int64_t NHD = (Hq + 2 * Hkv) * D;
-  auto dqkv = empty_rows(B * S, NHD, out_pad, q.options());
-  auto res = attn_bwd_impl(dout, q, k, v, o, lse, causal ? 1 : 0, scale, 3, c10::nullopt, c10::nullopt, c10::nullopt,
-                           bfm(dqkv), NHD + out_pad, cos.data_ptr<float>(), sin.data_ptr<float>());
-  const at::Tensor& dkp = std::get<1>(res);
-  const at::Tensor& dvp = std::get<2>(res);
+  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), D = q.size(3), Hkv = k.size(1);
   MX_OK(mx_rope_merge_bwd(nullptr, dkp.data_ptr<float>(), dvp.data_ptr<float>(), cos.data_ptr<float>(),
                           sin.data_ptr<float>(), bfm(dqkv), (int)B, (int)S, (int)Hq, (int)Hkv, (int)dkp.size(1), (int)D,
-                          NHD + out_pad, cur_stream(), (int)Hq));
+                          dqkv.stride(0), cur_stream(), (int)Hq));
   return dqkv;
-}
-
-// timing-only ablation variants (mode: -1 = causal without dQ atomics)
-std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd_ablate(const at::Tensor& dout, const at::Tensor& q,
-                                                               const at::Tensor& k, const at::Tensor& v,
-                                                               const at::Tensor& o, const at::Tensor& lse,
-                                                               int64_t mode, double scale) {
-  return attn_bwd_impl(dout, q, k, v, o, lse, (int)mode, scale, 1);
 }
 
 // ---------------------------------------------------------------- decode
@@ -1650,7 +1652,6 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("lora_grads(Tensor x, Tensor dy, Tensor g, Tensor st, Tensor(a!) ga, Tensor(b!) gb, int[] splits, int r, bool accumulate) -> ()");
   m.def("lora_gather_shrink(Tensor x, Tensor ids, Tensor a_tab, Tensor(a!) partials) -> ()");
   m.def("lora_gather_expand_add_(Tensor(a!) y, Tensor partials, Tensor ids, Tensor b_tab, Tensor s_tab, int[] splits, int K) -> ()");
-  m.def("attn_bwd_ablate(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, int mode, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, int dq_mode=3, Tensor? dq_out=None, Tensor? dk_out=None, Tensor? dv_out=None) -> (Tensor, Tensor, Tensor)");
   m.def("attn_bwd_rope(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor cos, Tensor sin, int out_pad=0) -> Tensor");
 }
@@ -1688,7 +1689,6 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_bwd_rope", &attn_bwd_rope);
-  m.impl("attn_bwd_ablate", &attn_bwd_ablate);
   m.impl("rope_append", &rope_append);
   m.impl("decode_attn_partials", &decode_attn_partials);
   m.impl("skinny_merge_linear", &skinny_merge_linear);

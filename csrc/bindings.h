@@ -8,21 +8,19 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "kernels/attn_args.h"
 #include "kernels/gemm8_args.h"
 #include "kernels/prefill_paged_args.h"
 #include "kernels/skinny_args.h"
 
 extern "C" {
-// attn_bwd.hip
-int mx_attn_bwd_partial_heads(int B, int Hq, int Hkv, int S, int Sk, int D, int dq_mode);
-int mx_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* o, const uint16_t* dout,
-                const float* lse, float* delta, float* dq, float* dkp, float* dvp, int B, int Hq, int Hkv, int S,
-                int Sk, int D, int causal, float scale, int dq_mode, void* work, int64_t ldo, hipStream_t stream,
-                uint16_t* dqkv, int64_t ldq, const float* cosb, const float* sinb);
+// attn_bwd.hip (operand rules: mx::ab_takes, kernels/attn_args.h)
+// sets L.hpw (mx::ab_hpw under MXLLM_ATTN_BWD8 / _HPW) and returns the dK / dV partial heads per batch row
+int mx_attn_bwd_partial_heads(mx::AbLaunch& L);
+int mx_attn_bwd(const mx::AbLaunch& L, float scale, hipStream_t stream);
 
-// attn_fwd.hip
-int mx_attn_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int Hq,
-                int Hkv, int S, int Sk, int D, int causal, float scale, int ldo, hipStream_t stream);
+// attn_fwd.hip (operand rules: mx::af_takes, kernels/attn_args.h)
+int mx_attn_fwd(const mx::AfLaunch& L, float scale, hipStream_t stream);
 
 // cross_entropy.hip
 int mx_ce_fwd_bwd(uint16_t* logits, const int64_t* labels, float* losses, float* inv_n, float* loss_out, int64_t T,

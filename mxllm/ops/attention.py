@@ -52,7 +52,15 @@ _DS_BUDGET = float(os.environ.get("MXLLM_ATTN_DS_BUDGET_GB", "4")) * 2**30
 
 
 def _ds_bytes_per_head(S: int, Sk: int) -> int:
+    """The dS^T image of one q head in the split mode: ``mx::ab_work_bytes`` per (batch row, q head)
+    (csrc/kernels/attn_args.h; tests/test_attn_args.py holds the two together)."""
     return (Sk + 127) // 128 * 128 * ((S + 63) // 64 * 64) * 2
+
+
+def attn_bwd_takes_rope(mode: int, D: int, S: int, Sk: int) -> bool:
+    """Whether ``attn_bwd_rope`` takes the backward (``mx::ab_takes_rope``): split mode, D = 128,
+    self-attention."""
+    return mode == 3 and D == 128 and Sk == S
 
 
 def backward_dqkv(do, q, k, v, o, lse, cos, sin, causal: bool, grad_pad: int = 0) -> torch.Tensor:
@@ -66,7 +74,7 @@ def backward_dqkv(do, q, k, v, o, lse, cos, sin, causal: bool, grad_pad: int = 0
     Hkv, Sk = k.shape[1], k.shape[2]
     scale = 1.0 / math.sqrt(D)
     mode = dq_mode()
-    if (mode == 3 and D == 128 and Sk == S and B * Hq * _ds_bytes_per_head(S, Sk) <= _DS_BUDGET
+    if (attn_bwd_takes_rope(mode, D, S, Sk) and B * Hq * _ds_bytes_per_head(S, Sk) <= _DS_BUDGET
             and os.environ.get("MXLLM_ATTN_DQ_ROPE", "1") != "0"):
         return ops.attn_bwd_rope(do.contiguous(), q, k, v, o, lse, causal, scale, cos, sin, grad_pad)
     dq, dkp, dvp = attn_bwd(do.contiguous(), q, k, v, o, lse, causal, scale, mode)
