@@ -1143,6 +1143,99 @@ std::tuple<at::Tensor, at::Tensor> decode_attn_partials(const at::Tensor& q, con
   return {sp.ml, sp.po};
 }
 
+// ---------------------------------------------------------------- verify attention (speculative decoding)
+// Decode attention for n consecutive query rows per sequence (csrc/kernels/decode.hip verify_attn):
+// q [B * n, Hq, 128], row b * n + j at position lens[b] + j of slot slots[b], j < nq[b]; the rows' K/V
+// are in the cache already -> out [B * n, Hq * 128]; rows j >= nq[b] are zeros.  `out` given: its first
+// B * n rows are written, the rest is left alone.  Pools: bf16 caches, or kv8 code pools with their
+// scale pools.  mx::vf_takes (kernels/verify_args.h) is THE check: it
+// runs before anything is allocated or enqueued, so a refused call writes nothing.
+static at::Tensor verify_attn_call(const char* op, const at::Tensor& q, const at::Tensor& k_pool,
+                                   const c10::optional<at::Tensor>& k_scale, const at::Tensor& v_pool,
+                                   const c10::optional<at::Tensor>& v_scale, const at::Tensor& lens,
+                                   const at::Tensor& nq, const c10::optional<at::Tensor>& slots, int64_t n,
+                                   int64_t max_len, double scale, const c10::optional<at::Tensor>& block_table,
+                                   const c10::optional<at::Tensor>& out_) {
+  const bool kv8 = k_scale.has_value();
+  MX_CHECK(q.is_cuda() && q.dim() == 3 && q.is_contiguous(), op, ": q must be a contiguous GPU tensor [B * n, Hq, D]");
+  MX_CHECK(n >= 1 && q.size(0) % n == 0, op, ": q has ", q.size(0), " rows, not a multiple of n = ", n);
+  const int64_t B = q.size(0) / n, Hq = q.size(1), D = q.size(2);
+  MX_CHECK(k_pool.dim() == 4 && v_pool.dim() == 4 && k_pool.sizes() == v_pool.sizes() && k_pool.is_contiguous() &&
+               v_pool.is_contiguous() && k_pool.device() == q.device() && v_pool.device() == q.device() &&
+               k_pool.scalar_type() == v_pool.scalar_type() && k_pool.size(3) == D,
+           op, ": K and V pools must be contiguous [rows, Hkv, SEQ, D] tensors of one shape and type on q's device");
+  const int64_t Hkv = k_pool.size(1), max_seq = k_pool.size(2);
+  if (kv8)
+    for (const at::Tensor* s : {&*k_scale, &*v_scale})
+      MX_CHECK(s->device() == q.device() && s->is_contiguous() && s->dim() == 3 && s->size(0) == k_pool.size(0) &&
+                   s->size(1) == Hkv && s->size(2) == max_seq && s->scalar_type() == at::kFloat,
+               op, ": scale pools must be contiguous float32 [rows, Hkv, SEQ] matching the code pools");
+  MX_CHECK(lens.defined() && nq.defined(), op, ": lens and nq");
+  mx::VfLaunch L{};
+  L.lens = check_rows_i32(lens, q.device(), B, op, "lens");
+  L.nq = check_rows_i32(nq, q.device(), B, op, "nq");
+  L.slots = check_rows_i32(slots, q.device(), B, op, "slots");
+  if (block_table.has_value() && block_table->defined()) {
+    const at::Tensor& t = *block_table;
+    MX_CHECK(t.device() == q.device() && t.scalar_type() == at::kInt && t.dim() == 2 && t.is_contiguous(), op,
+             ": block_table must be a contiguous int32 [slots, max_blocks] tensor on q's device");
+    L.bt = t.data_ptr<int32_t>();
+    L.maxb = t.size(1);
+  }
+  L.q = q.data_ptr();
+  L.k_pool = k_pool.data_ptr();
+  L.v_pool = v_pool.data_ptr();
+  L.k_scale = kv8 ? k_scale->data_ptr<float>() : nullptr;
+  L.v_scale = kv8 ? v_scale->data_ptr<float>() : nullptr;
+  const bool has_out = out_.has_value() && out_->defined();
+  if (has_out)
+    MX_CHECK(out_->device() == q.device() && out_->dim() == 2 && out_->is_contiguous() && out_->size(0) >= q.size(0) &&
+                 out_->size(1) == Hq * D,
+             op, ": out must be contiguous [>= B * n, Hq * D] rows on q's device");
+  L.q_bf16 = q.scalar_type() == at::kBFloat16;
+  L.out_bf16 = has_out ? out_->scalar_type() == at::kBFloat16 : L.q_bf16;
+  L.kv_bf16 = k_pool.scalar_type() == at::kBFloat16;
+  L.kv_u8 = k_pool.scalar_type() == at::kByte;
+  L.B = B, L.n = n, L.Hq = Hq, L.Hkv = Hkv, L.D = D;
+  L.rows = k_pool.size(0), L.max_seq = max_seq;
+  const int64_t cap = L.bt ? L.maxb * max_seq : max_seq;  // positions a sequence can hold
+  L.nsplit = std::max<int64_t>(1, (std::min(max_len, cap) + 255) / 256);  // decode_splits' plan
+  // the check runs on placeholders of the partials and the output first: nothing is allocated for a refused call
+  L.part_ml = L.part_o = reinterpret_cast<float*>(q.data_ptr());
+  L.out = q.data_ptr();
+  MX_CHECK(B > 0 && mx::vf_takes(L), op, ": the kernel does not take this call (mx::vf_takes, csrc/kernels/verify_args.h): B ",
+           B, ", n ", n, ", Hq ", Hq, ", Hkv ", Hkv, ", D ", D, ", SEQ ", max_seq, ", maxb ", L.maxb, ", nsplit ", L.nsplit,
+           kv8 ? ", kv8 pools" : ", pools of q's type");
+  DevGuard g(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  at::Tensor ml = at::empty({B * n, Hq, L.nsplit, 2}, f32), po = at::empty({B * n, Hq, L.nsplit, D}, f32);
+  at::Tensor out = has_out ? *out_ : at::empty({B * n, Hq * D}, q.options());
+  L.part_ml = ml.data_ptr<float>();
+  L.part_o = po.data_ptr<float>();
+  L.out = out.data_ptr();
+  MX_OK(mx_verify_attn(L, (float)scale, cur_stream()));
+  return out;
+}
+
+at::Tensor verify_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& lens,
+                       const at::Tensor& nq, const c10::optional<at::Tensor>& slots, int64_t n, int64_t max_len,
+                       double scale, const c10::optional<at::Tensor>& block_table,
+                       const c10::optional<at::Tensor>& out) {
+  MX_CHECK(k_cache.scalar_type() != at::kByte, "verify_attn: u8 code pools need their scale pools (verify_attn_kv8)");
+  return verify_attn_call("verify_attn", q, k_cache, c10::nullopt, v_cache, c10::nullopt, lens, nq, slots, n, max_len,
+                          scale, block_table, out);
+}
+
+at::Tensor verify_attn_kv8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& k_scale,
+                           const at::Tensor& v_codes, const at::Tensor& v_scale, const at::Tensor& lens,
+                           const at::Tensor& nq, const c10::optional<at::Tensor>& slots, int64_t n, int64_t max_len,
+                           double scale, const c10::optional<at::Tensor>& block_table,
+                           const c10::optional<at::Tensor>& out) {
+  MX_CHECK(k_codes.scalar_type() == at::kByte, "verify_attn_kv8: code pools must be uint8 [rows, Hkv, SEQ, 128]");
+  return verify_attn_call("verify_attn_kv8", q, k_codes, k_scale, v_codes, v_scale, lens, nq, slots, n, max_len, scale,
+                          block_table, out);
+}
+
 at::Tensor sample(const at::Tensor& logits, double temperature, int64_t seed, int64_t step) {
   MX_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "logits [B, V] contiguous GPU");
   MX_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16/f32");
@@ -1198,6 +1291,26 @@ at::Tensor sample_rows(const at::Tensor& logits, const at::Tensor& temps, const 
                        (int)B, (int)logits.size(1), temps.data_ptr<float>(), top_p.data_ptr<float>(),
                        top_k.data_ptr<int32_t>(), seeds.data_ptr<int64_t>(), steps.data_ptr<int32_t>(),
                        cur_stream()));
+  return out;
+}
+
+// acceptance of deterministic drafts (sampling.hip spec_accept_kernel): drawn, tokens int64 [B, n],
+// nq int32 [B] -> int32 [B, n + 1] = (accepted drafts, the emitted tokens, -1 padding)
+at::Tensor spec_accept(const at::Tensor& drawn, const at::Tensor& tokens, const at::Tensor& nq) {
+  MX_CHECK(drawn.is_cuda() && drawn.is_contiguous() && drawn.dim() == 2 && drawn.scalar_type() == at::kLong &&
+               drawn.size(1) >= 1,
+           "spec_accept: drawn must be a contiguous int64 [B, n] GPU tensor");
+  MX_CHECK(tokens.device() == drawn.device() && tokens.is_contiguous() && tokens.scalar_type() == at::kLong &&
+               tokens.sizes() == drawn.sizes(),
+           "spec_accept: tokens must be a contiguous int64 [B, n] tensor on drawn's device");
+  const int64_t B = drawn.size(0), n = drawn.size(1);
+  MX_CHECK(B <= 0x7fffffff / (n + 1), "spec_accept: B * (n + 1) must fit 31 bits");
+  MX_CHECK(nq.defined(), "spec_accept: nq");
+  const int32_t* np = check_rows_i32(nq, drawn.device(), B, "spec_accept", "nq");
+  DevGuard g(drawn.device());
+  auto out = at::empty({B, n + 1}, drawn.options().dtype(at::kInt));
+  MX_OK(mx_spec_accept(drawn.data_ptr<int64_t>(), tokens.data_ptr<int64_t>(), np, out.data_ptr<int32_t>(), (int)B,
+                       (int)n, cur_stream()));
   return out;
 }
 
@@ -1632,6 +1745,9 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("kv8_quant_rows(Tensor x) -> (Tensor, Tensor)");
   m.def("rope_append_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_codes, Tensor(b!) k_scale, Tensor(c!) v_codes, Tensor(d!) v_scale, int Hq, int Hkv, Tensor? block_table=None) -> Tensor");
   m.def("decode_attn_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> Tensor");
+  m.def("verify_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor nq, Tensor? slots, int n, int max_len, float scale, Tensor? block_table=None, Tensor? out=None) -> Tensor");
+  m.def("verify_attn_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor lens, Tensor nq, Tensor? slots, int n, int max_len, float scale, Tensor? block_table=None, Tensor? out=None) -> Tensor");
+  m.def("spec_accept(Tensor drawn, Tensor tokens, Tensor nq) -> Tensor");
   m.def("skinny_merge_linear(Tensor ml, Tensor po, Tensor w) -> Tensor");
   m.def("sample(Tensor logits, float temperature, int seed, int step) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor temps, Tensor top_p, Tensor top_k, Tensor seeds, Tensor steps) -> Tensor");
@@ -1697,6 +1813,9 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("kv8_quant_rows", &kv8_quant_rows);
   m.impl("rope_append_kv8", &rope_append_kv8);
   m.impl("decode_attn_kv8", &decode_attn_kv8);
+  m.impl("spec_accept", &spec_accept);
+  m.impl("verify_attn", &verify_attn);
+  m.impl("verify_attn_kv8", &verify_attn_kv8);
   m.impl("sample", &sample);
   m.impl("sample_rows", &sample_rows);
   m.impl("sample_temp_rows", &sample_temp_rows);

@@ -12,6 +12,7 @@
 #include "kernels/gemm8_args.h"
 #include "kernels/prefill_paged_args.h"
 #include "kernels/skinny_args.h"
+#include "kernels/verify_args.h"
 
 extern "C" {
 // attn_bwd.hip (operand rules: mx::ab_takes, kernels/attn_args.h)
@@ -47,6 +48,8 @@ int mx_decode_attn_kv8(const uint16_t* q, const uint8_t* kq, const float* ks, co
                        const int32_t* lens, int len_off, const int32_t* slots, float* part_ml, float* part_o,
                        uint16_t* out, int B, int Hq, int Hkv, int max_seq, int nsplit, float scale, const int32_t* bt,
                        int maxb, hipStream_t stream);
+// verify_attn / verify_attn_kv8 (operand rules: mx::vf_takes, kernels/verify_args.h)
+int mx_verify_attn(const mx::VfLaunch& L, float scale, hipStream_t stream);
 int64_t mx_sample_ws_floats(int B);
 int mx_sample(const void* logits, int is_bf16, int64_t* out, int B, int V, float temperature, uint32_t seed,
               uint32_t step, float* ws, hipStream_t stream);
@@ -158,6 +161,9 @@ int mx_rope_merge_bwd(const float* dq, const float* dkp, const float* dvp, const
 // sampling.hip
 int mx_sample_rows(const void* logits, int is_bf16, int64_t* out, int B, int V, const float* temps,
                    const float* top_ps, const int32_t* top_ks, const int64_t* seeds, const int32_t* steps,
+                   hipStream_t stream);
+
+int mx_spec_accept(const int64_t* drawn, const int64_t* tokens, const int32_t* nq, int32_t* out, int B, int n,
                    hipStream_t stream);
 
 // skinny_gemm.hip (operand rules of every entry: mx::sk_takes, kernels/skinny_args.h; the same

@@ -7,6 +7,8 @@
 //   * decode_combine : merges the per-split (m, l, o) partials;
 //   * kv8_quant_rows / rope_append_kv8 / decode_attn_kv8 : the same append and attention
 //                   over an fp8 (e4m3) cache with one power-of-two scale per row;
+//   * verify_attn : decode_attn for up to n consecutive query rows per sequence (speculative
+//                   decoding), both cache formats: the K/V are streamed once for all the rows;
 //   * sample : greedy argmax or exact temperature sampling via Gumbel-max with
 //              a counter-based hash RNG (one pass, no softmax materialised).
 // KV cache layout per layer: [slots, Hkv, max_seq, D] bf16 (contiguous per slot
@@ -110,6 +112,9 @@ __device__ __forceinline__ float ld_part(const float* p, int ld) {
 struct DecodeSplit {
   int split, hk, b, rep, slot, k_lo, k_hi;
   float* pml;
+  // verify_attn only (verify_split_begin): n rows per sequence in the launch, nq of them in use,
+  // row j sees keys 0 .. len0 + j - 1
+  int n, nq, len0;
 };
 // false for an empty split (workgroup-uniform), whose neutral partial is stored here (mode st)
 __device__ __forceinline__ bool decode_split_begin(DecodeSplit& s, const int32_t* __restrict__ lens, int len_off,
@@ -292,12 +297,15 @@ __device__ __forceinline__ int dswz(int row) { return ((row & 3) << 2) | ((row >
 //   * q_col(s, g): the first of the 8 dimensions that k-step s covers for lane group g (the MFMA
 //     summation order of the format);
 //   * score(x, j, i): x times the format's factor for key wk0 + 16 j + 4 g + i;
-//   * kQFirst: Q is loaded before K (the order of the loads as each format was tuned).
+//   * kQFirst: Q is loaded before K (the order of the loads as each format was tuned);
+//   * kMergeFma: the wave merge accumulates O with fused multiply-adds (true) or rounds each
+//     product first (false): the arithmetic each format's decode kernel has always had, now
+//     written out so that every instantiation of the body over the format has it.
 //
 // bf16 cache: K rows go straight from HBM into the A fragments (16 B per lane), V rows to LDS by
 // LDS-DMA (16 x 1-KiB lane-linear pieces; swizzle by permuting each lane's SOURCE chunk).
 struct KvBf16 {
-  static constexpr bool kQFirst = true;
+  static constexpr bool kQFirst = true, kMergeFma = true;
   const uint16_t* kc;
   const uint16_t* vc;
   u16x8 kf[4][4];
@@ -330,15 +338,32 @@ struct KvBf16 {
 };
 
 // one split of a decode-attention kernel over a cache of format KV: (m, l, o) partial of 256 keys
-// for every q-head of the GQA group (see the header comment above), stored in mode st
-template <class KV>
+// for every column of the (sequence, KV head) (see the header comment above), stored in mode st.
+// The 16 MFMA columns of a block are the q-heads of the GQA group (ROWS = false: decode, one query
+// row per sequence, NB = 1), or (query row j, head h) pairs, column col = j * rep + h over NB blocks
+// of 16 (ROWS = true: verify_attn).  A column has its own key limit (row j sees keys < len0 + j),
+// its own Q row and its own partial, (m, l, o) of q row b * n + j; the blocks share the K fragments
+// and the V image and have separate score and output accumulators.  Keys past a column's limit
+// but inside the split are real rows: their scores are replaced by -inf, their P is exactly 0.
+template <class KV, int NB = 1, bool ROWS = false>
 __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q, KV& kv, float* __restrict__ part_o,
-                                                  const DecodeSplit& ds, char* smem, float (*mls)[2][16], int Hq,
+                                                  const DecodeSplit& ds, char* smem, float (*mls)[2][16 * NB], int Hq,
                                                   int Hkv, int nsplit, int max_seq, float sl,
                                                   const int32_t* __restrict__ bt, int maxb, int st) {
-  constexpr int D = 128, ROWB = 256, WKEYS = 64, WTILE = WKEYS * ROWB;
+  // Every instantiation rounds alike: nothing here is contracted by the compiler's choice (which
+  // differs between instantiations -- a packed multiply in one, a fused multiply-add in the
+  // next); where the kernels have always fused, the fma is written out (the wave merge below).
+#pragma clang fp contract(off)
+  static_assert(ROWS || NB == 1, "decode: one block of columns");
+  constexpr int D = 128, ROWB = 256, WKEYS = 64, WTILE = WKEYS * ROWB, NC = 16 * NB;
   const int b = ds.b, hk = ds.hk, rep = ds.rep, split = ds.split, k_lo = ds.k_lo, k_hi = ds.k_hi;
   float* pml = ds.pml;
+  const int ncols = ROWS ? ds.n * rep : rep;
+  // (q row, head) index of column col: where its Q row, its partial and its output live
+  auto col_bh = [&](int col) -> int64_t {
+    if constexpr (ROWS) return ((int64_t)b * ds.n + col / rep) * Hq + hk * rep + col % rep;
+    else return (int64_t)b * Hq + hk * rep + col;
+  };
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
@@ -349,59 +374,85 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
   kv.load_v(rb, wk0, k_hi, lane, vs);
   if constexpr (!KV::kQFirst) kv.load_k(rb, wk0, k_hi, c, g);
   // Q^T fragments (B operand): lane (c, g), k-step s holds Q[head c][q_col(s, g) .. +7]
-  u16x8 qf[4];
-  const uint16_t* qrow = q + ((int64_t)b * Hq + hk * rep + min(c, rep - 1)) * D;
+  // klim: the keys that this lane's column sees end here (a column past ncols or of a row that is
+  // not in use sees none)
+  u16x8 qf[NB][4];
+  int klim[NB];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    qf[s] = *reinterpret_cast<const u16x8*>(qrow + KV::q_col(s, g));
-    if (c >= rep) qf[s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  for (int nb = 0; nb < NB; ++nb) {
+    const int col = 16 * nb + c;
+    bool on = col < ncols;
+    klim[nb] = k_hi;
+    if constexpr (ROWS) {
+      const int j = col / rep;
+      on = on && j < ds.nq;
+      klim[nb] = on ? min(k_hi, ds.len0 + j) : 0;
+    }
+    const uint16_t* qrow = q + col_bh(min(col, ncols - 1)) * D;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      qf[nb][s] = *reinterpret_cast<const u16x8*>(qrow + KV::q_col(s, g));
+      if (!on) qf[nb][s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
   }
   if constexpr (KV::kQFirst) kv.load_k(rb, wk0, k_hi, c, g);
-  f32x4 sacc[4];
+  f32x4 sacc[NB][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < 4; ++s) sacc[j] = mfma16(kv.k_frag(j, s), qf[s], sacc[j]);
+    for (int nb = 0; nb < NB; ++nb) sacc[nb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const u16x8 kf = kv.k_frag(j, s);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) sacc[nb][j] = mfma16(kf, qf[nb][s], sacc[nb][j]);
+    }
   }
   // Nothing is scheduled across this point, so every load of the split is in flight before the
   // softmax.  Loads to here and softmax are one basic block, and without the barrier the scheduler
   // sinks two of KvFp8's V loads (and their scales) to just before finish_v, where nothing hides
   // their latency.
   __builtin_amdgcn_sched_barrier(0);
-  // softmax over this wave's 64 keys, per head (= lane column c); lane (c, g)
+  // softmax over this wave's 64 keys, per column (= lane column c of each block); lane (c, g)
   // holds keys wk0 + 16 j + 4 g + i
-  float mx = -INFINITY;
+  float mx[NB], ls[NB];
+  u16x8 pb[NB][2];
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+  for (int nb = 0; nb < NB; ++nb) {
+    float m = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int key = wk0 + 16 * j + 4 * g + i;
-      const float x = key < k_hi ? kv.score(sacc[j][i], j, i) * sl : -INFINITY;
-      sacc[j][i] = x;
-      mx = fmaxf(mx, x);
-    }
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float mref = mx == -INFINITY ? 0.f : mx;  // wave with no valid key: all p = 0
-  float ls = 0.f;
-  u16x8 pb[2];
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+      for (int i = 0; i < 4; ++i) {
+        const int key = wk0 + 16 * j + 4 * g + i;
+        const float x = key < klim[nb] ? kv.score(sacc[nb][j][i], j, i) * sl : -INFINITY;
+        sacc[nb][j][i] = x;
+        m = fmaxf(m, x);
+      }
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float mref = m == -INFINITY ? 0.f : m;  // wave with no valid key: all p = 0
+    float l = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float p = __builtin_amdgcn_exp2f(sacc[j][i] - mref);
-      ls += p;
-      pb[j >> 1][4 * (j & 1) + i] = f2bf(p);
-    }
-  ls += __shfl_xor(ls, 16, 64);
-  ls += __shfl_xor(ls, 32, 64);
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = __builtin_amdgcn_exp2f(sacc[nb][j][i] - mref);
+        l += p;
+        pb[nb][j >> 1][4 * (j & 1) + i] = f2bf(p);
+      }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    mx[nb] = m, ls[nb] = l;
+  }
 
-  // O^T[d][head] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}.  Only this wave
+  // O^T[d][column] += V^T . P; k-step t covers keys 32 t + {16 h + 4 g + i}.  Only this wave
   // reads its image, and a wave's LDS operations complete in order.
-  f32x4 oacc[8];
+  f32x4 oacc[NB][8];
 #pragma unroll
-  for (int db = 0; db < 8; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int db = 0; db < 8; ++db) oacc[nb][db] = f32x4{0.f, 0.f, 0.f, 0.f};
   kv.finish_v(lane, vs);
   const int qq = c >> 2, pp = c & 3;
 #pragma unroll
@@ -413,23 +464,27 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
       const u16x4 va = tr_read16(vs + r0 * ROWB + 16 * (ch ^ dswz(r0)) + 8 * (pp & 1));
       const u16x4 vb = tr_read16(vs + r1 * ROWB + 16 * (ch ^ dswz(r1)) + 8 * (pp & 1));
       const u16x8 a = u16x8{va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-      oacc[db] = mfma16(a, pb[t], oacc[db]);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) oacc[nb][db] = mfma16(a, pb[nb][t], oacc[nb][db]);
     }
   }
   // merge the four waves: each wave parks (m, l, O^T) in its own V region
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's transposed reads retired
-  float* so = reinterpret_cast<float*>(vs);  // [d][16 heads]
+  float* so = reinterpret_cast<float*>(vs);  // [d][NC columns]: NB = 2 fills the wave's 16 KiB
 #pragma unroll
-  for (int db = 0; db < 8; ++db)
+  for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) so[(16 * db + 4 * g + i) * 16 + c] = oacc[db][i];
-  if (g == 0) {
-    mls[w][0][c] = mx;
-    mls[w][1][c] = ls;
+    for (int db = 0; db < 8; ++db)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) so[(16 * db + 4 * g + i) * NC + 16 * nb + c] = oacc[nb][db][i];
+    if (g == 0) {
+      mls[w][0][16 * nb + c] = mx[nb];
+      mls[w][1][16 * nb + c] = ls[nb];
+    }
   }
   __syncthreads();
-  for (int idx = tid; idx < rep * D; idx += 256) {
-    const int h = idx / D, d = idx % D;
+  for (int idx = tid; idx < ncols * D; idx += 256) {
+    const int h = idx / D, d = idx % D;  // h: the column
     float M = -INFINITY;
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) M = fmaxf(M, mls[ww][0][h]);
@@ -438,13 +493,18 @@ __device__ __forceinline__ void decode_split_body(const uint16_t* __restrict__ q
     for (int ww = 0; ww < 4; ++ww) {
       const float mw = mls[ww][0][h];
       const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-      L += f * mls[ww][1][h];
-      acc += f * reinterpret_cast<const float*>(smem + ww * WTILE)[d * 16 + h];
+      const float ow = reinterpret_cast<const float*>(smem + ww * WTILE)[d * NC + h];
+      L = __builtin_fmaf(f, mls[ww][1][h], L);
+      if constexpr (KV::kMergeFma) acc = __builtin_fmaf(f, ow, acc);
+      else acc = acc + f * ow;
     }
-    st_part(&part_o[(((int64_t)b * Hq + hk * rep + h) * nsplit + split) * D + d], acc, st);
+    const int64_t bh = col_bh(h);
+    st_part(&part_o[(bh * nsplit + split) * D + d], acc, st);
     if (d == 0) {
-      st_part(&pml[(int64_t)h * nsplit * 2], M, st);
-      st_part(&pml[(int64_t)h * nsplit * 2 + 1], L, st);
+      // ROWS: pml is split `split` of (row 0, head 0); decode: of the group's first head
+      float* ml = ROWS ? pml + bh * nsplit * 2 : pml + (int64_t)h * nsplit * 2;
+      st_part(&ml[0], M, st);
+      st_part(&ml[1], L, st);
     }
   }
 }
@@ -687,7 +747,7 @@ __global__ void __launch_bounds__(256) rope_append_kv8_kernel(
 //     transposed reads expect.
 // Keys at or past k_hi are never loaded, codes or scales: the index is clamped to k_hi - 1.
 struct KvFp8 {
-  static constexpr bool kQFirst = false;
+  static constexpr bool kQFirst = false, kMergeFma = false;
   const uint8_t* kq;
   const float* ksc;
   const uint8_t* vq;
@@ -747,6 +807,73 @@ __global__ void __launch_bounds__(256, 2) decode_attn_kv8_kernel(
   if (!decode_split_begin(ds, lens, len_off, slots, part_ml, Hq, Hkv, nsplit, 0)) return;
   KvFp8 kv{kq, ksc, vq, vsc};
   decode_split_body(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, 0);
+}
+
+// ---------------------------------------------------------------------------
+// verify_attn: decode attention for up to n consecutive query rows per sequence (speculative
+// decoding: the rows are the last accepted token and the drafts that follow it).  Sequence b has
+// nq[b] rows (0 .. n) at positions L_b .. L_b + nq[b] - 1 of its slot, L_b = lens[b]; their K/V are
+// already appended; row j sees keys 0 .. L_b + j.  q [B * n, Hq, 128]: row b * n + j.
+// The kernel is decode_split_body with ROWS = true: the K/V of a (sequence, KV head) are streamed
+// once for all its rows (decode_attn over the same rows streams them once per row).  Grid
+// (nsplit, Hkv, B) as decode; the split range comes from the longest row.  NB = 1: n * rep <= 16
+// columns, NB = 2: <= 32.  Partials (m, l, o) of q row b * n + j in decode's format, merged by
+// decode_combine_kernel; rows j >= nq[b] get partials that combine to zeros.  Columns are
+// independent and masked probabilities are exactly 0, so row j equals decode_attn /
+// decode_attn_kv8 of that row as a sequence of its own (same slot, lens = L_b + j, len_off 1, same
+// nsplit) bit for bit.
+// nq[b] is clamped into [0, n] and L_b into [0, capacity - nq[b]]: no key at or past the slot's
+// capacity is ever addressed.
+// Resources (hipcc -O3 --offload-arch=gfx950, the metadata of the generated assembly; LDS = 4 x 16 KiB
+// V images + mls; decode_attn_mfma_kernel has 96 VGPRs, decode_attn_kv8_kernel 123):
+//   KvBf16 NB = 1:  97 VGPRs, 0 B scratch, 66048 B LDS     KvBf16 NB = 2: 161 VGPRs, 0 B scratch, 66560 B LDS
+//   KvFp8  NB = 1: 126 VGPRs, 0 B scratch, 66048 B LDS     KvFp8  NB = 2: 162 VGPRs, 0 B scratch, 66560 B LDS
+// All within the 256 VGPRs of __launch_bounds__(256, 2): two workgroups per CU, as decode.
+__device__ __forceinline__ bool verify_split_begin(DecodeSplit& s, const int32_t* __restrict__ lens,
+                                                   const int32_t* __restrict__ nq,
+                                                   const int32_t* __restrict__ slots, float* __restrict__ part_ml,
+                                                   int Hq, int Hkv, int n, int nsplit, int cap) {
+  s.split = blockIdx.x, s.hk = blockIdx.y, s.b = blockIdx.z;
+  s.rep = Hq / Hkv;
+  s.n = n;
+  s.nq = min(max(nq[s.b], 0), min(n, cap));
+  const int L = max(min(lens[s.b], cap - s.nq), 0);
+  s.len0 = L + 1;
+  s.slot = slots ? slots[s.b] : s.b;
+  s.k_lo = s.split * kSplit;
+  s.k_hi = min(s.nq ? L + s.nq : 0, s.k_lo + kSplit);  // a sequence without rows streams nothing
+  s.pml = part_ml + (int64_t)s.split * 2;
+  if (s.k_lo < s.k_hi) return true;
+  const int tid = threadIdx.x;
+  if (tid < n * s.rep) {
+    float* ml = s.pml + (((int64_t)s.b * n + tid / s.rep) * Hq + s.hk * s.rep + tid % s.rep) * nsplit * 2;
+    ml[0] = -INFINITY;
+    ml[1] = 0.f;
+  }
+  return false;
+}
+
+// k / v: bf16 pools (KvBf16; ksc = vsc = nullptr) or e4m3 code pools with their scale pools (KvFp8)
+template <class KV, int NB>
+__global__ void __launch_bounds__(256, 2) verify_attn_kernel(
+    const uint16_t* __restrict__ q, const void* __restrict__ k, const float* __restrict__ ksc,
+    const void* __restrict__ v, const float* __restrict__ vsc, const int32_t* __restrict__ lens,
+    const int32_t* __restrict__ nq, const int32_t* __restrict__ slots, float* __restrict__ part_ml,
+    float* __restrict__ part_o, int Hq, int Hkv, int n, int max_seq, int nsplit, float sl,
+    const int32_t* __restrict__ bt, int maxb) {
+  constexpr int WTILE = 64 * 256;  // 16 KiB per wave
+  __shared__ __attribute__((aligned(16))) char smem[4 * WTILE];
+  __shared__ float mls[4][2][16 * NB];
+  DecodeSplit ds;
+  const int cap = bt ? maxb * max_seq : max_seq;
+  if (!verify_split_begin(ds, lens, nq, slots, part_ml, Hq, Hkv, n, nsplit, cap)) return;
+  if constexpr (std::is_same<KV, KvFp8>::value) {
+    KvFp8 kv{(const uint8_t*)k, ksc, (const uint8_t*)v, vsc};
+    decode_split_body<KvFp8, NB, true>(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, 0);
+  } else {
+    KvBf16 kv{(const uint16_t*)k, (const uint16_t*)v};
+    decode_split_body<KvBf16, NB, true>(q, kv, part_o, ds, smem, mls, Hq, Hkv, nsplit, max_seq, sl, bt, maxb, 0);
+  }
 }
 
 // logits [B, V] (bf16 or f32); temperature <= 0 -> greedy.  out ids [B] int64.
@@ -917,6 +1044,28 @@ extern "C" int mx_decode_attn_kv8(const uint16_t* q, const uint8_t* kq, const fl
   decode_attn_kv8_kernel<<<grid, 256, 0, stream>>>(q, kq, ks, vq, vs, lens, len_off, slots, part_ml, part_o, Hq, Hkv,
                                                    max_seq, nsplit, scale * 1.4426950408889634f, bt, maxb);
   decode_combine_kernel<128><<<B * Hq, 128, 0, stream>>>(part_ml, part_o, out, nsplit);
+  return (int)hipGetLastError();
+}
+
+// verify_attn over bf16 or kv8 pools (operand rules: mx::vf_takes, kernels/verify_args.h)
+extern "C" int mx_verify_attn(const mx::VfLaunch& L, float scale, hipStream_t stream) {
+  if (L.B <= 0) return 0;
+  if (!vf_takes(L)) return -1;
+  const dim3 grid((unsigned)L.nsplit, (unsigned)L.Hkv, (unsigned)L.B);
+  const float sl = scale * 1.4426950408889634f;
+  const bool two = L.n * (L.Hq / L.Hkv) > 16;
+#define VA(KV, NB)                                                                                                   \
+  verify_attn_kernel<KV, NB><<<grid, 256, 0, stream>>>(                                                              \
+      (const uint16_t*)L.q, L.k_pool, L.k_scale, L.v_pool, L.v_scale, L.lens, L.nq, L.slots, L.part_ml, L.part_o,    \
+      (int)L.Hq, (int)L.Hkv, (int)L.n, (int)L.max_seq, (int)L.nsplit, sl, L.bt, (int)L.maxb)
+  if (L.kv_u8) {
+    if (two) VA(KvFp8, 2); else VA(KvFp8, 1);
+  } else {
+    if (two) VA(KvBf16, 2); else VA(KvBf16, 1);
+  }
+#undef VA
+  decode_combine_kernel<128><<<(unsigned)(L.B * L.n * L.Hq), 128, 0, stream>>>(L.part_ml, L.part_o, (uint16_t*)L.out,
+                                                                               (int)L.nsplit);
   return (int)hipGetLastError();
 }
 

@@ -226,6 +226,29 @@ __global__ void __launch_bounds__(kSampThreads) sample_topkp_kernel(
   if (threadIdx.x == 0) out[row] = gi < V ? gi : bi;
 }
 
+// Acceptance of deterministic drafts (speculative decoding; the proposal is one-hot, so exact
+// speculative sampling is "the draw equals the draft").  Sequence b fed tokens[b][0 .. nq[b] - 1] to
+// its rows (row 0: its last token, rows 1..: the drafts) and drew drawn[b][j] on row j.  Draft j + 1
+// is accepted iff every row before it was and drawn[b][j] == tokens[b][j + 1].  out [B, n + 1]:
+// out[b][0] = a, the number of accepted drafts (-1 for nq[b] <= 0), out[b][1 .. a + 1] = the tokens
+// the step emits (the draws of rows 0 .. a: the accepted drafts, then the correction or bonus
+// token), the rest -1.  One thread per sequence.
+__global__ void __launch_bounds__(64) spec_accept_kernel(const int64_t* __restrict__ drawn,
+                                                         const int64_t* __restrict__ tokens,
+                                                         const int32_t* __restrict__ nq, int32_t* __restrict__ out,
+                                                         int B, int n) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int m = min(nq[b], n);
+  const int64_t* dr = drawn + (int64_t)b * n;
+  const int64_t* tk = tokens + (int64_t)b * n;
+  int32_t* o = out + (int64_t)b * (n + 1);
+  int a = 0;
+  while (a + 1 < m && dr[a] == tk[a + 1]) ++a;
+  o[0] = m > 0 ? a : -1;
+  for (int j = 0; j < n; ++j) o[1 + j] = m > 0 && j <= a ? (int32_t)dr[j] : -1;
+}
+
 }  // namespace mx
 
 using namespace mx;
@@ -244,5 +267,14 @@ extern "C" int mx_sample_rows(const void* logits, int is_bf16, int64_t* out, int
   else
     sample_topkp_kernel<float><<<B, kSampThreads, 0, stream>>>((const float*)logits, out, V, temps, top_ps, top_ks,
                                                                seeds, steps);
+  return (int)hipGetLastError();
+}
+
+// drawn, tokens int64 [B, n], nq int32 [B] -> out int32 [B, n + 1] (spec_accept_kernel)
+extern "C" int mx_spec_accept(const int64_t* drawn, const int64_t* tokens, const int32_t* nq, int32_t* out, int B,
+                              int n, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (n <= 0 || !drawn || !tokens || !nq || !out) return -1;
+  spec_accept_kernel<<<(B + 63) / 64, 64, 0, stream>>>(drawn, tokens, nq, out, B, n);
   return (int)hipGetLastError();
 }

@@ -1,7 +1,8 @@
 """Inference ops: prefill attention into a KV cache, decode attention, sampling.
 
 GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, their kv8
-forms over an fp8 KV cache, greedy / Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature),
+forms over an fp8 KV cache, the multi-row verify attention of speculative decoding,
+greedy / Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature, draft acceptance),
 logits_proc.hip (sampling penalties, logit_bias, log-probabilities),
 attn_fwd.hip for prefill and prefill_paged.hip for prefill chunks over the paged cache.
 CPU: reference implementations.
@@ -311,6 +312,111 @@ def decode_attention(qkv: torch.Tensor, cos, sin, k_cache, v_cache, pos: torch.T
         sc = torch.einsum("hd,hld->hl", qi, kk) / math.sqrt(D)
         outs.append(torch.einsum("hl,hld->hd", sc.softmax(-1), vv).reshape(-1))
     return torch.stack(outs).to(qkv.dtype)
+
+
+# ---------------------------------------------------------------- speculative decoding: verify + accept
+def verify_attn(q: torch.Tensor, k_cache, v_cache, lens, nq, slots, n: int, max_len: int, scale: float,
+                block_table: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                v_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """Decode attention for up to ``n`` consecutive query rows per sequence.  q [B * n, Hq, D]: row
+    ``b * n + j`` is the query at position ``lens[b] + j`` of cache slot ``slots[b]`` (None: b), for
+    ``j < nq[b]``; the rows' K/V are in the cache already and row j sees keys 0 .. lens[b] + j.
+    -> [B * n, Hq * D]; rows ``j >= nq[b]`` are zeros.  ``k_scale`` / ``v_scale``: kv8 pools.
+
+    GPU: ``verify_attn`` / ``verify_attn_kv8`` (csrc/kernels/decode.hip): the K/V of a sequence are
+    streamed once for all its rows, and row j is bit for bit ``decode_attn`` / ``decode_attn_kv8`` of
+    that row as a sequence of its own (lens[b] + j, len_off 1, the same ``max_len``).  bf16,
+    head_dim 128, n * (Hq / Hkv) <= 32 (``mx::vf_takes``); anything else is an error.
+    CPU: the fp32 softmax expression per row (kv8: over the dequantised rows)."""
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("verify_attn: a kv8 cache needs both k_scale and v_scale")
+    if use_native(q):
+        if k_scale is not None:
+            return native().verify_attn_kv8(q, k_cache, k_scale, v_cache, v_scale, lens, nq, slots, n, max_len, scale,
+                                            block_table)
+        return native().verify_attn(q, k_cache, v_cache, lens, nq, slots, n, max_len, scale, block_table)
+    R, Hq, D = q.shape
+    if n < 1 or R % n:
+        raise ValueError(f"verify_attn: q has {R} rows, not a multiple of n = {n}")
+    deq = _kv8_codec()[1] if k_scale is not None else None
+    bt = block_table.cpu() if block_table is not None else None
+    Hkv = k_cache.shape[1]
+    out = torch.zeros(R, Hq * D, dtype=q.dtype)
+    for b in range(R // n):
+        L0, s = int(lens[b]), int(slots[b]) if slots is not None else b
+        for j in range(min(max(int(nq[b]), 0), n)):
+            L = L0 + j + 1
+            kk, vv = _kv_at(k_cache, bt, s, 0, L), _kv_at(v_cache, bt, s, 0, L)
+            if deq is not None:
+                kk, vv = deq(kk, _kv_at(k_scale, bt, s, 0, L)), deq(vv, _kv_at(v_scale, bt, s, 0, L))
+            kk, vv = kk.float().repeat_interleave(Hq // Hkv, 0), vv.float().repeat_interleave(Hq // Hkv, 0)
+            sc = torch.einsum("hd,hld->hl", q[b * n + j].float(), kk) * scale
+            out[b * n + j] = torch.einsum("hl,hld->hd", sc.softmax(-1), vv).reshape(-1).to(q.dtype)
+    return out
+
+
+def verify_attention(qkv: torch.Tensor, cos, sin, k_cache, v_cache, pos: torch.Tensor, slots: torch.Tensor,
+                     lens: torch.Tensor, nq: torch.Tensor, seq_slots: torch.Tensor, n: int, Hq: int, Hkv: int, D: int,
+                     max_len: int, block_table: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                     v_scale: torch.Tensor | None = None, q: torch.Tensor | None = None) -> torch.Tensor:
+    """The attention of a verify step: ``n`` rows per sequence, qkv [B * n, NH*D].  ``pos`` /
+    ``slots`` int32 [B * n]: where each ROW's K/V are appended (a row that is not in use points at a
+    scratch slot); ``lens`` / ``nq`` / ``seq_slots`` int32 [B]: each SEQUENCE's length before the
+    step, its rows in use and its slot.  RoPE and the cache append of every row (``rope_append`` /
+    ``rope_append_kv8``), then ``verify_attn``.  ``q``: the rotated queries when the QKV GEMM's
+    epilogue has done the RoPE and the append already."""
+    scale = 1.0 / math.sqrt(D)
+    if q is None:
+        if k_scale is not None:
+            if D != 128:
+                raise ValueError(f"verify_attention: the fp8 KV cache supports head_dim 128 only, got {D}")
+            q = rope_append_kv8(qkv, cos, sin, pos, slots, k_cache, k_scale, v_cache, v_scale, Hq, Hkv, block_table)
+        elif use_native(qkv):
+            q = native().rope_append(qkv.contiguous(), cos, sin, pos, slots, k_cache, v_cache, Hq, Hkv, D, block_table)
+        else:  # decode_attention's CPU expression: q stays fp32, K rounded to the cache's type
+            R = qkv.shape[0]
+            x = qkv.view(R, Hq + 2 * Hkv, D).float()
+            c, sn = cos[pos.long()].view(R, 1, D // 2).float(), sin[pos.long()].view(R, 1, D // 2).float()
+
+            def rot(t):
+                t1, t2 = t[..., : D // 2], t[..., D // 2:]
+                return torch.cat([t1 * c - t2 * sn, t2 * c + t1 * sn], -1)
+
+            q, kr = rot(x[:, :Hq]), rot(x[:, Hq:Hq + Hkv])
+            bt = block_table.cpu() if block_table is not None else None
+            for r in range(R):
+                p, s = int(pos[r]), int(slots[r])
+                _kv_at(k_cache, bt, s, p, p + 1)[:, 0] = kr[r].to(k_cache.dtype)
+                _kv_at(v_cache, bt, s, p, p + 1)[:, 0] = x[r, Hq + Hkv:].to(v_cache.dtype)
+            return verify_attn(q, k_cache, v_cache, lens, nq, seq_slots, n, max_len, scale, block_table).to(qkv.dtype)
+    return verify_attn(q, k_cache, v_cache, lens, nq, seq_slots, n, max_len, scale, block_table, k_scale, v_scale)
+
+
+def spec_accept(drawn: torch.Tensor, tokens: torch.Tensor, nq: torch.Tensor) -> torch.Tensor:
+    """Acceptance of deterministic drafts.  Sequence b fed ``tokens[b, :nq[b]]`` to its rows (row 0:
+    its last token, rows 1..: the drafts) and drew ``drawn[b, j]`` on row j.  The proposal is one-hot,
+    so exact speculative sampling reduces to: draft j + 1 is accepted iff every row before it was
+    and ``drawn[b, j] == tokens[b, j + 1]``.  drawn, tokens int64 [B, n], nq int32 [B] ->
+    int32 [B, n + 1]: ``out[b, 0] = a``, the number of accepted drafts (-1 for ``nq[b] <= 0``),
+    ``out[b, 1 : a + 2]`` the tokens the step emits (the draws of rows 0 .. a: the accepted drafts,
+    then the correction or bonus token), the rest -1.  GPU: csrc/kernels/sampling.hip."""
+    if drawn.dim() != 2 or tokens.shape != drawn.shape or nq.numel() != drawn.shape[0]:
+        raise ValueError("spec_accept: drawn and tokens [B, n], nq [B]")
+    if use_native(drawn):
+        return native().spec_accept(drawn.to(torch.long).contiguous(), tokens.to(drawn.device, torch.long).contiguous(),
+                                    nq.to(drawn.device, torch.int32).contiguous())
+    B, n = drawn.shape
+    out = torch.full((B, n + 1), -1, dtype=torch.int32)
+    for b in range(B):
+        m = min(int(nq[b]), n)
+        if m <= 0:
+            continue
+        a = 0
+        while a + 1 < m and int(drawn[b, a]) == int(tokens[b, a + 1]):
+            a += 1
+        out[b, 0] = a
+        out[b, 1:a + 2] = drawn[b, :a + 1].to(torch.int32)
+    return out
 
 
 def sample(logits: torch.Tensor, temperature: float = 0.0, seed: int = 0, step: int = 0,

@@ -33,6 +33,15 @@ is then [4, B] (the fourth row: each row's adapter table slot, -1 = none) and gr
 (batch bucket, key bucket, any_adapter): a step in which no row has an adapter replays the same
 fused launches as an engine without tables; a step with adapters runs every projection unfused
 followed by the two gather kernels of ``ops.lora_delta_rows_``.
+
+Speculative decoding (``speculate=K``, off by default): a decode step may carry up to K + 1 rows of one
+sequence -- its last token and up to K drafted tokens (mxllm/serve/speculate.py: prompt lookup, no
+second model).  The rows run through the same projections (the weights are streamed once), each row's
+K/V are appended at its own position, ``dops.verify_attention`` streams the sequence's K/V once for all
+its rows, the sampler draws on every row and ``dops.spec_accept`` keeps the drafts the draws confirm.
+The drafts are deterministic, so this is exact speculative sampling: the token stream is the plain
+engine's.  Such a step is replayed from a graph keyed ("verify", row bucket, key bucket, K + 1) beside
+the keys above; a step in which no request has a draft, or some row has a LoRA adapter, is the plain step.
 """
 from __future__ import annotations
 
@@ -148,6 +157,7 @@ class Request:
     adapter: str | None = None  # name of a loaded LoRA adapter (Engine.load_adapter); None = the base model
     cached_tokens: int = 0  # prompt tokens served from the prefix cache (Engine(prefix_cache=True))
     prefilled: int = 0      # prompt positions whose K/V are in the cache (paged prefill: cached + computed chunks)
+    spec_index: object = None  # speculative decoding: the request's n-gram index (mxllm/serve/speculate.py)
 
     def __post_init__(self):
         # any penalty / logit_bias / logprobs: the request takes the adjusted sampling path
@@ -159,7 +169,7 @@ class Engine:
                  use_graphs: bool | None = None, prefill_tokens: int = 16384, tp_group=None,
                  kv_pool_tokens: int | None = None, kv_block: int = 256, kv_dtype: str | None = None,
                  max_adapters: int = 0, max_lora_rank: int = 16, prefix_cache: bool | None = None,
-                 prefill_chunk: int | None = None):
+                 prefill_chunk: int | None = None, speculate: int | None = None, drafter=None):
         """``tp_group``: serve a tensor-parallel shard (mxllm/parallel/tensor.py
         ``shard_llama`` / ``random_shard``) with the other ranks of the group;
         every rank of the group runs the same schedule (same submissions in the
@@ -185,7 +195,28 @@ class Engine:
         every prefill runs through ``prefill_segments`` (``dops.prefill_attention_paged``: attention
         of a chunk over the rows already in the block pool); with both off nothing changes.
         Neither works with ``kv_dtype="fp8"`` or ``tp_group`` yet (ValueError).  Two new requests of
-        ONE admission pass that share a prefix both miss: blocks are registered when a prompt completes."""
+        ONE admission pass that share a prefix both miss: blocks are registered when a prompt completes.
+        ``speculate`` = K (None: env MXLLM_SPECULATE; 0 / None: off): speculative decoding with up to K
+        drafted tokens per request and step (``verify``; the module docstring).  ``drafter``: any
+        callable ``(tokens: list[int], k: int) -> list[int]`` that proposes at most k tokens to follow
+        ``tokens`` (prompt + output); None: prompt lookup, kept incrementally per request
+        (mxllm/serve/speculate.py).  Requests with penalties, logit_bias or logprobs get no drafts, a
+        step with a LoRA row is the plain step, and tensor parallelism is not supported yet (ValueError).
+        (K + 1) * (n_heads / n_kv_heads) must not exceed 32, the columns of the verify kernel."""
+        if speculate is None and os.environ.get("MXLLM_SPECULATE"):
+            speculate = int(os.environ["MXLLM_SPECULATE"])
+        speculate = int(speculate or 0)
+        if speculate < 0:
+            raise ValueError(f"speculate must be >= 0, got {speculate}")
+        if speculate and tp_group is not None:
+            raise ValueError("speculate is not supported under tensor parallelism (tp_group) yet")
+        if speculate:
+            group = model.cfg.n_heads // model.cfg.n_kv_heads
+            if (speculate + 1) * group > 32:
+                raise ValueError(f"speculate={speculate}: {speculate + 1} rows of {group} q-heads per KV head exceed the "
+                                 f"32 columns of the verify kernel; this model allows speculate <= {32 // group - 1}")
+        self.speculate = speculate
+        self.drafter = drafter
         if max_adapters < 0:
             raise ValueError(f"max_adapters must be >= 0, got {max_adapters}")
         if max_adapters > 0 and tp_group is not None:
@@ -233,7 +264,12 @@ class Engine:
         self.scratch_slot = max_batch  # padding rows of a graphed step write here
         c = self.cfg
         dt = model.tok_emb.dtype
-        n_slots = max_batch + (1 if self.use_graphs else 0)
+        # the spare slot: padding rows of a graphed step, and of a verify step, write there
+        spare = self.use_graphs or bool(speculate)
+        n_slots = max_batch + (1 if spare else 0)
+        if speculate and self.device.type == "cuda" and (c.head_dim != 128 or dt != torch.bfloat16):
+            raise ValueError(f"speculate: the verify kernel takes bf16 models of head_dim 128; this one is {dt}, "
+                             f"head_dim {c.head_dim}")
         if kv_pool_tokens is None and os.environ.get("MXLLM_KV_POOL_TOKENS"):
             kv_pool_tokens = int(os.environ["MXLLM_KV_POOL_TOKENS"])
         from .kvcache import KV_DTYPES, KVCache
@@ -251,7 +287,7 @@ class Engine:
             raise ValueError("prefix_cache needs the paged KV cache (kv_pool_tokens / MXLLM_KV_POOL_TOKENS)")
         self.kv = KVCache(c.n_layers, c.n_kv_heads, c.head_dim, dt, self.device, n_slots, self.max_seq,
                           pool_tokens=kv_pool_tokens, block=kv_block,
-                          scratch_slot=self.scratch_slot if self.use_graphs else None, kv_dtype=kv_dtype,
+                          scratch_slot=self.scratch_slot if spare else None, kv_dtype=kv_dtype,
                           prefix_cache=self.prefix_cache)
         # MXLLM_DECODE_COMBINE=fused: the split-K partials merge inside the attention launch (the
         # last workgroup of each (seq, kv-head) combines; these counters stay zero between calls)
@@ -301,6 +337,9 @@ class Engine:
         self.prefix_query_tokens = 0  # prompt tokens of requests admitted with the prefix cache on
         self.prefix_hit_tokens = 0    # ... of which served from cached blocks
         self.prefill_chunks = 0       # segments run by prefill_segments in step()
+        self.spec_steps = 0             # verify steps
+        self.spec_draft_tokens = 0      # drafted tokens verified
+        self.spec_accepted_tokens = 0   # ... of which accepted
 
     # ------------------------------------------------------------------ model pieces
     def _norm_proj(self, delta, h, gamma, lin, swiglu: bool):
@@ -620,6 +659,17 @@ class Engine:
             return dops.decode_attention(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], pos, sl,
                                          c.n_heads, c.n_kv_heads, c.head_dim, max_len, bt, cnt)
 
+        qkv_fn = self._qkv_rope_fn(pos, sl)
+        xn = self._layers(x, attn, qkv_fn if lora is None else None, lora=lora)
+        return self._logits(xn)
+
+    def _qkv_rope_fn(self, pos: torch.Tensor, sl: torch.Tensor):
+        """``_layers``' ``qkv_fn`` of a decode or verify step whose rows are appended at position
+        ``pos[r]`` of slot ``sl[r]``: what it fuses depends on the rows of the step, not on its
+        sequences (``ops.qkv_rope_linear`` / ``qkv_rope_ok`` look at h)."""
+        m, c = self.model, self.cfg
+        bt, fp8 = self.kv.bt, self.kv.fp8
+
         def qkv_fn(i, delta, h, gamma, layer):
             # QKV GEMM with the RoPE/cache-append epilogue; 1-2 rows also with the RMSNorm prologue
             # (one launch), more rows after the RMSNorm kernel
@@ -643,8 +693,7 @@ class Engine:
             q, _ = ops.qkv_rope_linear(None, xn, None, c.norm_eps, *rope)
             return q, h
 
-        xn = self._layers(x, attn, qkv_fn if lora is None else None, lora=lora)
-        return self._logits(xn)
+        return qkv_fn
 
     def _buckets(self, B: int, max_len: int) -> tuple[int, int]:
         bb = 1
@@ -701,6 +750,165 @@ class Engine:
         self._graphs[(bb, kl, any_adapter)] = (inp, out, graph, host)
         log.debug("captured decode graph: batch %d, key bound %d, adapters %s", bb, kl, any_adapter)
         return self._graphs[(bb, kl, any_adapter)]
+
+    # ------------------------------------------------------------------ speculative decoding
+    @torch.no_grad()
+    def verify(self, slots: list[int], rows: list[list[int]]):
+        """One verify step: ``rows[i]`` are the tokens at positions ``lens[s] ..`` of ``slots[i]`` -- the
+        sequence's last token and its drafts, 1 .. speculate + 1 of them.  Every row's K/V are appended
+        at its position and row j attends over keys 0 .. lens[s] + j.  Returns (logits [B * n, V], the
+        rows' tokens [B, n] and the sequences' row counts [B] on the device, what ``dops.spec_accept``
+        takes); n = speculate + 1, sequence i's row j at ``i * n + j`` (rows past ``len(rows[i])`` are padding).
+        ``lens`` is NOT advanced: the caller keeps what it accepts (``lens[s] += accepted + 1``); the
+        K/V rows of rejected drafts stay behind as stale rows past ``lens``, which nothing reads and
+        the next step overwrites (kv8: codes and scales alike)."""
+        n, B = self.speculate + 1, len(slots)
+        if n < 2:
+            raise ValueError("verify: the engine was built without speculate")
+        if any(not 1 <= len(r) <= n for r in rows) or len(rows) != B:
+            raise ValueError(f"verify: 1 .. {n} rows per sequence")
+        if self.lora is not None and any(self.slot_adapter[s] >= 0 for s in slots):
+            raise ValueError("verify: sequences on a LoRA adapter take the plain step")
+        for s_, r in zip(slots, rows):
+            self._ensure(s_, self.lens[s_] + len(r))
+        max_len = max(self.lens[s_] + len(r) for s_, r in zip(slots, rows))
+        if self.use_graphs:
+            bb, kl = self._buckets(B, max_len)
+            entry = self._graphs.get(("verify", bb, kl, n)) or self._capture_verify(bb, kl, n)
+            inp, out, graph, host = entry
+        else:
+            bb = B
+            host = torch.empty(3 * bb * (n + 1), dtype=torch.long)
+        # host: (token, position, slot) of every row [3, bb * n], then (base length, rows in use, slot) of
+        # every sequence [3, bb]; rows not in use: token 0, position 0, the spare slot
+        rv, sv = host[:3 * bb * n].view(3, bb, n), host[3 * bb * n:].view(3, bb)
+        rv[0].zero_()
+        rv[1].zero_()
+        rv[2].fill_(self.scratch_slot)
+        sv[0].zero_()
+        sv[1].zero_()
+        sv[2].fill_(self.scratch_slot)
+        for i, (s_, r) in enumerate(zip(slots, rows)):
+            L, m = self.lens[s_], len(r)
+            rv[0, i, :m] = torch.tensor(r)
+            rv[1, i, :m] = torch.arange(L, L + m)
+            rv[2, i, :m] = s_
+            sv[0, i], sv[1, i], sv[2, i] = L, m, s_
+        if self.use_graphs:
+            inp.copy_(host, non_blocking=True)
+            graph.replay()
+        else:
+            inp = host.to(self.device)
+            out = self._verify_body(inp, bb, max_len, n)
+        return out[:B * n], inp[:bb * n].view(bb, n)[:B], inp[3 * bb * n + bb:3 * bb * n + 2 * bb][:B]
+
+    def _verify_body(self, inp: torch.Tensor, bb: int, max_len: int, n: int) -> torch.Tensor:
+        """inp int64 [3 * bb * n + 3 * bb]: ``verify``'s row and sequence tables.  A decode step over
+        bb * n rows whose attention is ``dops.verify_attention``.  The shortcuts of ``_decode_body``
+        that assume one row per sequence do not apply here: the split merge in the o-projection and
+        the in-launch combine counters are not used, and the fused QKV prologue / epilogue decide by
+        the rows of the step (``_qkv_rope_fn``)."""
+        m, c = self.model, self.cfg
+        rows, seq = inp[:3 * bb * n].view(3, bb * n), inp[3 * bb * n:].view(3, bb)
+        pos, sl = rows[1].to(torch.int32), rows[2].to(torch.int32)
+        lens, nq, ssl = seq[0].to(torch.int32), seq[1].to(torch.int32), seq[2].to(torch.int32)
+        x = ops.embedding(rows[0], m.tok_emb)
+        bt = self.kv.bt
+        scales = (lambda i: (self.kv.k_scale[i], self.kv.v_scale[i])) if self.kv.fp8 else (lambda i: (None, None))
+
+        def attn(i, qkv, q=None):
+            ks, vs = scales(i)
+            return dops.verify_attention(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], pos, sl, lens, nq, ssl,
+                                         n, c.n_heads, c.n_kv_heads, c.head_dim, max_len, bt, ks, vs, q=q)
+
+        xn = self._layers(x, attn, self._qkv_rope_fn(pos, sl))
+        return self._logits(xn)
+
+    def _capture_verify(self, bb: int, kl: int, n: int):
+        """One graph per (sequence bucket, key bucket, n): rows laid out [bb, n]."""
+        inp = torch.zeros(3 * bb * (n + 1), dtype=torch.long, device=self.device)
+        inp[2 * bb * n:3 * bb * n].fill_(self.scratch_slot)  # warm-up / capture traffic goes to the spare slot
+        inp[3 * bb * n + 2 * bb:].fill_(self.scratch_slot)
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(2):  # library handles / workspace set up outside capture
+                self._verify_body(inp, bb, kl, n)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        if self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
+        with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
+            out = self._verify_body(inp, bb, kl, n)
+        host = torch.empty(inp.shape[0], dtype=torch.long, pin_memory=True)
+        self._graphs[("verify", bb, kl, n)] = (inp, out, graph, host)
+        log.debug("captured verify graph: %d sequences x %d rows, key bound %d", bb, n, kl)
+        return self._graphs[("verify", bb, kl, n)]
+
+    def _drafts(self, reqs) -> list[list[int]]:
+        """At most ``min(speculate, remaining new tokens - 1)`` drafted tokens per request, and never a
+        position past what the slot holds; none for requests whose token state depends on every
+        earlier token (penalties, logit_bias, logprobs)."""
+        out = []
+        for r in reqs:
+            k = min(self.speculate, r.params.max_new_tokens - len(r.output) - 1,
+                    self.kv.capacity(r.slot) - self.lens[r.slot] - 2)
+            if k <= 0 or r.special:
+                out.append([])
+                continue
+            toks = r.prompt + r.output
+            if self.drafter is not None:
+                d = list(self.drafter(toks, k))[:k]
+            else:
+                if r.spec_index is None:
+                    from .speculate import NgramIndex
+
+                    r.spec_index = NgramIndex()
+                r.spec_index.sync(toks)
+                d = r.spec_index.propose(k)
+            d = [int(t) for t in d]
+            out.append(d if all(0 <= t < self.vocab for t in d) else [])  # (a drafter's stray id: no draft)
+        return out
+
+    def _verify_step(self, slots, reqs, drafts) -> None:
+        """The decode part of ``step`` when some request has a draft: one ``verify`` pass, the sampler
+        on every row (row j of a request draws with its step + j), ``spec_accept``, one read-back.
+        Requests with penalties, logit_bias or logprobs have one row, sampled by ``_sample`` on that row
+        (a step that carries such a request beside drafted ones reads back twice)."""
+        n, B = self.speculate + 1, len(reqs)
+        rows = [[r.output[-1]] + d for r, d in zip(reqs, drafts)]
+        logits, tokens, nq = self.verify(slots, rows)
+        self.steps += 1
+        self.spec_steps += 1
+        # sampling parameters per row; rows not in use draw greedily and are ignored
+        temps, top_ps, top_ks, seeds, steps = ([0.0] * (B * n), [1.0] * (B * n), [0] * (B * n), [0] * (B * n),
+                                               [0] * (B * n))
+        for i, (r, row) in enumerate(zip(reqs, rows)):
+            p = r.params
+            for j in range(len(row)):
+                k = i * n + j
+                temps[k], top_ps[k], top_ks[k], seeds[k] = p.temperature, p.top_p, p.top_k, p.seed
+                steps[k] = len(r.output) + j
+        special = [i for i, r in enumerate(reqs) if r.special]
+        sp_toks = {}
+        if special:  # one row each: the adjusted sampling path, on that row
+            idx = torch.tensor([i * n for i in special], device=logits.device)
+            sub = [reqs[i] for i in special]
+            sp_toks = dict(zip(special, self._sample(logits.index_select(0, idx), sub)))
+        drawn = dops.sample_rows(logits, temps, top_ps, top_ks, seeds, steps)
+        acc = dops.spec_accept(drawn.view(-1, n)[:B], tokens, nq).tolist()  # the step's read-back
+        for i, (r, d) in enumerate(zip(reqs, drafts)):
+            a = acc[i][0]
+            emitted = [sp_toks[i]] if i in sp_toks else acc[i][1:a + 2]
+            self.spec_draft_tokens += len(d)
+            self.spec_accepted_tokens += a if i not in sp_toks else 0
+            self.decode_tokens += len(emitted)
+            slot = r.slot
+            for t in emitted:  # one by one: streaming, stop and length handling are the plain step's
+                self.lens[slot] += 1
+                self._accept(r, int(t))
+                if r.done.is_set():
+                    break  # an EOS / stop / length inside the run: later tokens are dropped
 
     # ------------------------------------------------------------------ scheduling
     # ------------------------------------------------------------------ embeddings
@@ -833,7 +1041,9 @@ class Engine:
                 "decode_tokens_per_s": self.decode_tokens / self.decode_s if self.decode_s else 0.0,
                 "decode_steps": self.steps, "kv_cache_dtype": self.kv_dtype, "kv_cache_bytes": self.kv.nbytes(),
                 "lora_adapters": sorted(self.adapters), "prefix_cache_query_tokens": self.prefix_query_tokens,
-                "prefix_cache_hit_tokens": self.prefix_hit_tokens, "prefill_chunks": self.prefill_chunks}
+                "prefix_cache_hit_tokens": self.prefix_hit_tokens, "prefill_chunks": self.prefill_chunks,
+                "spec_steps": self.spec_steps, "spec_draft_tokens": self.spec_draft_tokens,
+                "spec_accepted_tokens": self.spec_accepted_tokens}
 
     def _finish(self, r: Request, reason: str):
         r.finish_reason = reason
@@ -1005,6 +1215,12 @@ class Engine:
         reqs = [self.active[s] for s in slots]
         t0 = time.perf_counter()
         tokens = torch.tensor([r.output[-1] for r in reqs], dtype=torch.long)
+        if self.speculate and not (self.lora is not None and any(self.slot_adapter[s_] >= 0 for s_ in slots)):
+            drafts = self._drafts(reqs)
+            if any(drafts):
+                self._verify_step(slots, reqs, drafts)
+                self.decode_s += time.perf_counter() - t0
+                return True
         logits = self.decode(slots, tokens)
         self.steps += 1
         nxt = self._sample(logits, reqs)

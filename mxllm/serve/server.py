@@ -163,6 +163,9 @@ def build_app(engine: Engine, tokenizer, model_name: str, api_key: str | None = 
                  f"mxllm_prefix_cache_query_tokens_total {getattr(engine, 'prefix_query_tokens', 0)}",
                  f"mxllm_prefix_cache_hit_tokens_total {getattr(engine, 'prefix_hit_tokens', 0)}",
                  f"mxllm_prefill_chunks_total {getattr(engine, 'prefill_chunks', 0)}",
+                 f"mxllm_spec_steps_total {getattr(engine, 'spec_steps', 0)}",
+                 f"mxllm_spec_draft_tokens_total {getattr(engine, 'spec_draft_tokens', 0)}",
+                 f"mxllm_spec_accepted_tokens_total {getattr(engine, 'spec_accepted_tokens', 0)}",
                  f"mxllm_prefill_seconds_total {engine.prefill_s:.6f}",
                  f"mxllm_decode_tokens_total {engine.decode_tokens}",
                  f"mxllm_decode_seconds_total {engine.decode_s:.6f}",
@@ -304,7 +307,7 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
                   checkpoint: str | None = None, tokenizer_path: str | None = None, seed: int = 0,
                   weights: str = "bf16", tp_group=None, kv_cache: str | None = None, adapters: dict | None = None,
                   max_loras: int | None = None, max_lora_rank: int = 16, prefix_cache: bool | None = None,
-                  prefill_chunk: int | None = None, kv_pool_tokens: int | None = None):
+                  prefill_chunk: int | None = None, kv_pool_tokens: int | None = None, speculate: int | None = None):
     """Engine + tokenizer.  ``tp_group``: this rank serves its tensor-parallel
     shard (mxllm/parallel/tensor.py) of the model; the full model is built (or
     loaded) on the rank's GPU, sliced and freed.  ``kv_cache``: "bf16" / "fp8" KV cache
@@ -312,7 +315,8 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
     LoRA directory} served beside the base model (``max_loras`` table slots, default one per adapter,
     each of rank <= ``max_lora_rank``); a request whose ``model`` is such a name runs on that adapter.
     ``prefix_cache`` / ``prefill_chunk`` / ``kv_pool_tokens``: the engine's options of the same names
-    (None: their env variables)."""
+    (None: their env variables).  ``speculate`` = K: speculative decoding with up to K prompt-lookup
+    drafts per request and step (``Engine(speculate=K)``; None: env MXLLM_SPECULATE)."""
     from ..data.tokenizer import get_tokenizer
     from ..models import build_model, tokenizer_path_for
 
@@ -343,7 +347,8 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
     eng = Engine(m, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id, getattr(tok, "eos_id", cfg.eos_id)),
                  tp_group=tp_group, kv_dtype=kv_cache,
                  max_adapters=max(max_loras or 0, len(adapters or {})), max_lora_rank=max_lora_rank,
-                 prefix_cache=prefix_cache, prefill_chunk=prefill_chunk, kv_pool_tokens=kv_pool_tokens)
+                 prefix_cache=prefix_cache, prefill_chunk=prefill_chunk, kv_pool_tokens=kv_pool_tokens,
+                 speculate=speculate)
     for name, path in (adapters or {}).items():
         eng.load_adapter(name, path)
     return eng, tok
@@ -394,6 +399,10 @@ def parse_args(argv=None):
     ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
                     help="prefill at most N prompt tokens per engine step, so a long prompt does not stall the "
                          "streaming requests (bf16 KV cache, --tp 1; env MXLLM_PREFILL_CHUNK)")
+    ap.add_argument("--speculative-ngram", type=int, default=None, metavar="K",
+                    help="speculative decoding: verify up to K tokens per request and step, drafted by n-gram "
+                         "lookup in the request's own prompt and output (no draft model; --tp 1; K + 1 times the "
+                         "q-heads per KV head at most 32; env MXLLM_SPECULATE)")
     return ap.parse_args(argv)
 
 
@@ -413,7 +422,8 @@ def main(argv=None):
     eng, tok = build_default(a.model, None, a.max_batch, a.max_seq, a.checkpoint, a.tokenizer, weights=a.weights,
                              tp_group=group, kv_cache=a.kv_cache, adapters=parse_lora_modules(a.lora),
                              max_loras=a.max_loras, max_lora_rank=a.max_lora_rank, prefix_cache=a.prefix_cache,
-                             prefill_chunk=a.prefill_chunk, kv_pool_tokens=a.kv_pool_tokens)
+                             prefill_chunk=a.prefill_chunk, kv_pool_tokens=a.kv_pool_tokens,
+                             speculate=a.speculative_ngram)
     if group is not None:
         eng.enable_tp_sync()
         if env.rank != 0:
