@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--new-tokens", type=int, default=64)
     ap.add_argument("--e2e-prompt-len", type=int, default=256)
     ap.add_argument("--fp8", action="store_true", help="e4m3 projection weights (serving quantisation)")
+    ap.add_argument("--mxfp4", action="store_true",
+                    help="OCP MXFP4 projection weights: e2m1 codes, one e8m0 scale per 32 (serving quantisation)")
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--top-p", type=float, default=1.0, help="e2e requests: nucleus sampling (with --temperature)")
     ap.add_argument("--temperature", type=float, default=0.0)
@@ -54,6 +56,8 @@ def main():
     ap.add_argument("--tp-shard-proxy", type=int, default=0,
                     help="one GPU: run rank 0's TP-N shard without the collectives (per-GPU compute floor)")
     a = ap.parse_args()
+    if a.fp8 and a.mxfp4:
+        ap.error("--fp8 and --mxfp4 exclude each other")
 
     from mxllm.models import Llama, get_config
     from mxllm.serve.engine import Engine
@@ -87,10 +91,15 @@ def main():
         from mxllm.serve.quant import quantize_model_fp8_
 
         quantize_model_fp8_(model)
+    elif a.mxfp4:
+        from mxllm.serve.quant import quantize_model_mxfp4_
+
+        quantize_model_mxfp4_(model)
     torch.cuda.synchronize()
     init_s = time.perf_counter() - t0
     wbytes = sum(p.numel() * p.element_size() for p in model.parameters()) + \
-        sum(b.numel() * b.element_size() for n, b in model.named_buffers() if n.endswith((".q", ".scale")))
+        sum(b.numel() * b.element_size() for n, b in model.named_buffers()
+            if n.endswith((".q", ".scale", ".codes", ".scales")))
     bmax = max(int(b) for b in a.batches.split(","))
     max_seq = max(a.prompt_len, a.ctx + a.decode_steps, a.e2e_prompt_len + a.new_tokens) + 8
     eng = Engine(model, max_batch=max(bmax, 1), max_seq=max_seq, tp_group=tp_group, kv_pool_tokens=a.kv_pool_tokens,
@@ -111,7 +120,7 @@ def main():
         times.append(time.perf_counter() - t)
     del nxt
     pre_s = min(times)
-    out = {"model": a.model, "weights": "fp8-e4m3 projections" if a.fp8 else "bf16",
+    out = {"model": a.model, "weights": "fp8-e4m3 projections" if a.fp8 else "mxfp4 projections" if a.mxfp4 else "bf16",
            "tensor_parallel": ({"tp": world, "collectives": "RCCL all-reduce x2/layer + logits all-gather"}
                                if world > 1 else
                                {"tp": a.tp_shard_proxy, "collectives": "omitted (one-GPU shard proxy)"}

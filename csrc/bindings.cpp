@@ -1573,6 +1573,58 @@ at::Tensor w8_dequant(const at::Tensor& q, const at::Tensor& scale) {
   return w;
 }
 
+// ---------------------------------------------------------------- MXFP4 weights (serving)
+// codes u8 [N, K/2] (two e2m1 codes per byte, even k low), scales u8 [N, K/32] (e8m0): mxllm/serve/quant.py
+static void w4_weights(const char* op, const at::Tensor& codes, const at::Tensor& scales, const at::Device& dev) {
+  MX_CHECK(codes.is_cuda() && codes.device() == dev && codes.scalar_type() == at::kByte && codes.dim() == 2 &&
+               codes.is_contiguous(), op, ": codes must be contiguous uint8 [N, K/2] on the GPU");
+  MX_CHECK(scales.device() == dev && scales.scalar_type() == at::kByte && scales.dim() == 2 && scales.is_contiguous() &&
+               scales.size(0) == codes.size(0) && codes.size(1) % 16 == 0 && scales.size(1) == codes.size(1) / 16,
+           op, ": scales must be contiguous uint8 [N, K/32] beside codes [N, K/2], K % 32 == 0");
+}
+
+at::Tensor w4_dequant(const at::Tensor& codes, const at::Tensor& scales) {
+  w4_weights("w4_dequant", codes, scales, codes.device());
+  DevGuard g(codes.device());
+  const int64_t N = codes.size(0), K = 2 * codes.size(1);
+  auto w = at::empty({N, K}, codes.options().dtype(at::kBFloat16));
+  MX_OK(mx_w4_dequant(codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), bfm(w), N, K, cur_stream()));
+  return w;
+}
+
+// y[M, N] = x[M, K] . dequant(codes, scales)^T.  Up to 32 rows: one launch of the weight-streaming
+// kernel.  33 .. stream_m rows: ceil(M / 32) launches over 32-row slices of x and y (the 4-bit weights
+// are streamed that many times: at 64 rows as many bytes as one fp8 pass).  More rows, or a shape
+// mx::w4_takes refuses: dequantise into a bf16 temporary and run the hipBLASLt GEMM.  Nothing here
+// synchronises with the host, so all of it can be captured into a hipGraph.
+at::Tensor w4_linear(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales, int64_t stream_m) {
+  sk_rows("w4_linear", "x", x, x.device());
+  w4_weights("w4_linear", codes, scales, x.device());
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  MX_CHECK(2 * codes.size(1) == K, "w4_linear: x has ", K, " columns, the codes ", 2 * codes.size(1));
+  DevGuard g(x.device());
+  auto y = at::empty({M, N}, x.options());
+  if (M == 0 || N == 0) return y;
+  const int64_t ldx = M <= 1 ? K : x.stride(0);  // the stride of a one-row view is arbitrary
+  mx::W4Launch L{};
+  L.x = x.data_ptr(), L.ldx = ldx, L.codes = codes.data_ptr(), L.scales = scales.data_ptr();
+  L.y = y.data_ptr(), L.ldy = N;
+  L.M = std::min<int64_t>(M, mx::W4_MAX_M), L.N = N, L.K = K;
+  if (M <= std::max<int64_t>(stream_m, mx::W4_MAX_M) && mx::w4_takes(L)) {
+    for (int64_t m0 = 0; m0 < M; m0 += mx::W4_MAX_M) {
+      L.x = bf(x) + m0 * ldx, L.y = bfm(y) + m0 * N, L.M = std::min<int64_t>(M - m0, mx::W4_MAX_M);
+      const int rc = mx_w4a16_gemm(L, cur_stream());
+      MX_CHECK(rc != -1, "w4_linear: the kernel does not take this call (mx::w4_takes, csrc/kernels/w4_args.h): M ", L.M,
+               ", N ", N, ", K ", K, ", row stride x ", ldx);
+      TORCH_CHECK(rc == 0, "mxllm kernel launch failed (w4_linear) rc=", rc, " ", hipGetErrorString((hipError_t)rc));
+    }
+    return y;
+  }
+  auto w = at::empty({N, K}, x.options());
+  MX_OK(mx_w4_dequant(codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), bfm(w), N, K, cur_stream()));
+  return at::mm(x, w.t());
+}
+
 // ---------------------------------------------------------------- LoRA rank-r GEMMs
 // out[:, 0:Vrows] = alpha * x . v^T (x [M, K], v [Vrows, K] row views, Vrows % 64 == 0):
 // the forward s x A^T / backward s dy B products written into the augmented-GEMM tails.
@@ -1762,6 +1814,8 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("skinny_qkv_rope(Tensor h, Tensor? delta, Tensor? gamma, float eps, Tensor w, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_cache, Tensor(b!) v_cache, int Hq, int Hkv, Tensor? block_table=None) -> (Tensor, Tensor)");
   m.def("skinny_norm_linear(Tensor h, Tensor? delta, Tensor gamma, float eps, Tensor w, bool swiglu) -> (Tensor, Tensor)");
   m.def("w8_dequant(Tensor q, Tensor scale) -> Tensor");
+  m.def("w4_linear(Tensor x, Tensor codes, Tensor scales, int stream_m) -> Tensor");
+  m.def("w4_dequant(Tensor codes, Tensor scales) -> Tensor");
   m.def("quant_rows_e4m3(Tensor x) -> (Tensor, Tensor)");
   m.def("lora_xwt(Tensor x, Tensor v, Tensor(a!) out, float alpha, int rows=0) -> ()");
   m.def("swiglu_lora(Tensor? dm, Tensor gu, int pad, Tensor v, int nrb, float alpha) -> Tensor");
@@ -1828,6 +1882,8 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("skinny_qkv_rope", &skinny_qkv_rope);
   m.impl("skinny_norm_linear", &skinny_norm_linear);
   m.impl("w8_dequant", &w8_dequant);
+  m.impl("w4_linear", &w4_linear);
+  m.impl("w4_dequant", &w4_dequant);
   m.impl("quant_rows_e4m3", &quant_rows_e4m3);
   m.impl("lora_xwt", &lora_xwt);
   m.impl("swiglu_lora", &swiglu_lora);

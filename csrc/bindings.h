@@ -13,6 +13,7 @@
 #include "kernels/prefill_paged_args.h"
 #include "kernels/skinny_args.h"
 #include "kernels/verify_args.h"
+#include "kernels/w4_args.h"
 
 extern "C" {
 // attn_bwd.hip (operand rules: mx::ab_takes, kernels/attn_args.h)
@@ -77,6 +78,10 @@ int mx_w8a16_gemm(const uint16_t* x, int64_t ldx, const uint8_t* q, const float*
                   int M, int N, int K, hipStream_t stream);
 int mx_quant_rows_e4m3(const uint16_t* x, int64_t ldx, uint8_t* q, float* s, int64_t M, int K, hipStream_t stream);
 int mx_w8_dequant(const uint8_t* q, const float* scale, uint16_t* w, int64_t N, int K, hipStream_t stream);
+
+// mxfp4_gemm.hip (operand rules of the GEMM: mx::w4_takes, kernels/w4_args.h)
+int mx_w4a16_gemm(const mx::W4Launch& L, hipStream_t stream);
+int mx_w4_dequant(const uint8_t* codes, const uint8_t* scales, uint16_t* w, int64_t N, int64_t K, hipStream_t stream);
 
 // gemm8.hip (operand rules of every entry point: mx::g8_takes, kernels/gemm8_args.h)
 int mx_gemm8(const uint16_t* A, int64_t lda, int a_kc, const uint16_t* B, int64_t ldb, int b_kc, void* C,

@@ -403,7 +403,7 @@ class Engine:
         """``_layers`` for a pass with rows on LoRA adapters: ``lora(i, proj, y, x)`` adds the rows'
         deltas to the projection output y in place.  The unfused route -- RMSNorm kernel, projection,
         delta, ``attn_fn(i, qkv)``, SwiGLU kernel; no GEMM prologue or epilogue -- whatever the
-        projection's class (``FusedLinear``, ``W8Linear``)."""
+        projection's class (``FusedLinear``, ``W8Linear``, ``W4Linear``)."""
         m, c = self.model, self.cfg
         h, delta, gamma = x, None, m.layers[0].attn_norm
         for i, layer in enumerate(m.layers):

@@ -56,6 +56,10 @@ def ensure_local_engine(model_name: str, device, engine_model: str = "", max_bat
         from .quant import quantize_model_fp8_
 
         quantize_model_fp8_(model)
+    elif weights == "mxfp4":
+        from .quant import quantize_model_mxfp4_
+
+        quantize_model_mxfp4_(model)
     tok = get_tokenizer(cfg.vocab_size, tokenizer_path or None, cfg.bos_id, cfg.eos_id)
     max_seq = min(max_seq, cfg.max_seq_len)
     pool = kv_pool_tokens or max(max_batch * 4096, max_seq)

@@ -19,6 +19,11 @@ weight-only HIP kernel with bf16 activations; larger calls quantise the activati
 per token as well and use hipBLASLt's fp8 GEMM (``torch._scaled_mm``, row-wise
 scales).  Training never uses this path (the fine-tuning benchmark is bf16 end to
 end).
+
+MXFP4 (OCP Microscaling, 4.25 bits per weight; ``--weights mxfp4``) halves the weight
+bytes once more: the format, :func:`quantize_mxfp4`, :class:`W4Linear` and
+:func:`quantize_model_mxfp4_` are further down, the HIP kernel is
+``csrc/kernels/mxfp4_gemm.hip``.
 """
 from __future__ import annotations
 
@@ -123,6 +128,123 @@ class W8Linear(nn.Module):
             y = torch._scaled_mm(xq.view(torch.float8_e4m3fn), self.q.view(torch.float8_e4m3fn).t(), scale_a=sa,
                                  scale_b=self.scale.view(1, -1), out_dtype=x2.dtype)
         return y.view(*x.shape[:-1], self.out_features)
+
+
+# ---------------------------------------------------------------- MXFP4 projection weights
+# OCP Microscaling v1.0 "MXFP4" on a weight W [N, K], K % 32 == 0.  A block is 32 consecutive k of one
+# output channel; its shared scale is 2^e, stored as the e8m0 byte e + 127 with
+# e = floor(log2(amax |block|)) - 2 clamped to [-126, 127] (read from the float's exponent field), an
+# all-zero block as byte 127; bytes 0 and 255 are never emitted.  Elements are e2m1: magnitudes
+# {0, 0.5, 1, 1.5, 2, 3, 4, 6} as codes 0..7, bit 3 the sign.  |w| / 2^e (exact: a power of two) is
+# rounded to nearest on that grid, ties to the even code, saturating at 6 (the floor rule leaves
+# amax / 2^e in [4, 8)); the sign bit is set only on a non-zero magnitude, so there is no negative zero
+# and the quantiser is idempotent on its own output.  codes uint8 [N, K/2], the even k in the low nibble
+# (the packing of torch.float4_e2m1fn_x2); scales uint8 [N, K/32]; no second-level scale.
+# Every dequantised value +-grid * 2^e has at most two mantissa bits: the dequantised weight is a bf16
+# matrix (like the kv8 cache), which is what lets the HIP kernels (csrc/kernels/mxfp4_gemm.hip) be
+# tested bit for bit against these functions -- the reference, the CPU path and the load-time quantiser.
+# Cost of round-to-nearest MXFP4, measured on Gaussian rows: relative RMS weight error 0.114 .. 0.115,
+# about 2 % of the elements saturate.  End-task accuracy on real checkpoints has NOT been measured.
+MXFP4_BLOCK = 32
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+# w4_linear streams the 4-bit weights once per 32 rows, so a call of M rows costs ceil(M / 32) weight
+# passes; calls of more than STREAM_M rows dequantise into a bf16 temporary and run the hipBLASLt GEMM
+# instead.  The default is the largest M at which the passes still won on the Llama-3.1 70B projection
+# shapes (bench/w4_probe.py --crossover; table in profiles/mxfp4/README.md), passes / dequantise + GEMM in
+# us for the four projections of a layer: 32 rows 307 / 753, 64 rows 554 / 805 (qkv alone loses, 95 / 69),
+# 128 rows 1049 / 899, 256 rows 2046 / 1089.  Both routes are slower than the bf16 and fp8 engines at 64
+# rows (70B decode step 48.6 ms against 36.2 / 26.2 ms): the 32-row kernel is bound by its X traffic.
+STREAM_M = int(os.environ.get("MXLLM_W4_STREAM_M", "64"))
+
+
+def quantize_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """w [N, K] (finite, K % 32 == 0) -> (codes uint8 [N, K/2], scales uint8 [N, K/32])."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: [N, K] with K % {MXFP4_BLOCK} == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    wf = w.detach().float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    a = wf.abs()
+    bits = a.amax(-1).view(torch.int32)
+    e = ((bits >> 23) - 129).clamp_(-126, 127)  # floor(log2 amax) - 2; f32 subnormals clamp
+    e = torch.where(bits == 0, torch.zeros_like(e), e)
+    inv = ((127 - e) << 23).view(torch.float32)  # 2^-e, a normal f32 for every e in [-126, 125]
+    v = a * inv.unsqueeze(-1)
+    # nearest grid point, ties to the even code: the midpoints 0.25 1.25 2.5 5 round down, 0.75 1.75 3.5 up
+    code = ((v > 0.25).to(torch.uint8) + (v >= 0.75) + (v > 1.25) + (v >= 1.75) + (v > 2.5) + (v >= 3.5) + (v > 5.0))
+    code = code.to(torch.uint8)
+    code = code | (((wf < 0) & (code != 0)).to(torch.uint8) << 3)
+    code = code.reshape(N, K // 2, 2)
+    codes = code[..., 0] | (code[..., 1] << 4)
+    return codes.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Reference decode: codes uint8 [N, K/2], scales uint8 [N, K/32] (bytes 1..254) -> f32 [N, K]."""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    nib = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(N, K).to(torch.int64)
+    mag = torch.tensor(MXFP4_GRID, dtype=torch.float32, device=codes.device)[nib & 7]
+    v = torch.where((nib & 8) != 0, -mag, mag)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)  # 2^(byte - 127)
+    return (v.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * scale.unsqueeze(-1)).reshape(N, K)
+
+
+class W4Linear(nn.Module):
+    """Frozen projection y = x W^T with MXFP4 weights (serving only).  From a weight (quantised here)
+    or from ``codes`` / ``scales`` in the format above."""
+
+    def __init__(self, weight: torch.Tensor | None = None, *, codes: torch.Tensor | None = None,
+                 scales: torch.Tensor | None = None):
+        super().__init__()
+        if weight is not None:
+            if codes is not None or scales is not None:
+                raise ValueError("W4Linear: a weight, or codes and scales")
+            codes, scales = quantize_mxfp4(weight.detach())
+        if codes is None or scales is None or codes.dtype != torch.uint8 or scales.dtype != torch.uint8 \
+                or codes.dim() != 2 or scales.dim() != 2 or codes.shape[1] % 16 \
+                or tuple(scales.shape) != (codes.shape[0], codes.shape[1] // 16):
+            raise ValueError("W4Linear: codes uint8 [N, K/2] and scales uint8 [N, K/32], K % 32 == 0")
+        if bool(((scales == 0) | (scales == 255)).any()):
+            raise ValueError("W4Linear: scale bytes 0 (2^-127) and 255 (NaN) are not part of the format")
+        self.register_buffer("codes", codes.contiguous())
+        self.register_buffer("scales", scales.contiguous())
+        self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x2 = x.reshape(-1, self.in_features)
+        if x2.stride(1) != 1 or x2.stride(0) % 8:
+            x2 = x2.contiguous()  # the HIP kernel takes 16-B-aligned rows
+        if not use_native(x2):
+            y = torch.matmul(x2, dequantize_mxfp4(self.codes, self.scales).to(x2.dtype).t())
+        else:
+            # weight-streaming HIP kernel, one pass per 32 rows up to STREAM_M rows; beyond, and for
+            # shapes it does not take, w4_linear dequantises to bf16 and runs hipBLASLt
+            y = native().w4_linear(x2, self.codes, self.scales, STREAM_M)
+        return y.view(*x.shape[:-1], self.out_features)
+
+
+@torch.no_grad()
+def quantize_model_mxfp4_(model) -> int:
+    """Replace every transformer projection (qkv, o, gate/up, down) of a Llama whose ``in_features`` is a
+    multiple of 32 by a :class:`W4Linear` (LoRA adapters are merged first).  Embedding, norms and the LM
+    head stay bf16.  Returns the number of weight bytes saved."""
+    from ..models.llama import FusedLinear
+    from .engine import merge_lora_
+
+    merge_lora_(model)
+    saved = 0
+    for layer in model.layers:
+        for name in ("wqkv", "wo", "wgu", "wd"):
+            lin = getattr(layer, name)
+            if isinstance(lin, FusedLinear) and lin.weight.shape[1] % MXFP4_BLOCK == 0:
+                w = lin.weight
+                q = W4Linear(w)
+                setattr(layer, name, q)
+                saved += w.numel() * w.element_size() - q.codes.numel() - q.scales.numel()
+                del lin, w
+    if torch.cuda.is_available():
+        torch.cuda.empty_cache()
+    return saved
 
 
 @torch.no_grad()

@@ -343,6 +343,10 @@ def build_default(model: str = "tiny", device: str | None = None, max_batch: int
         from .quant import quantize_model_fp8_
 
         quantize_model_fp8_(m)
+    elif weights == "mxfp4":  # after shard_llama: a TP rank quantises its own slice
+        from .quant import quantize_model_mxfp4_
+
+        quantize_model_mxfp4_(m)
     tok = get_tokenizer(cfg.vocab_size, tokenizer_path, cfg.bos_id, cfg.eos_id)
     eng = Engine(m, max_batch=max_batch, max_seq=max_seq, eos_ids=(cfg.eos_id, getattr(tok, "eos_id", cfg.eos_id)),
                  tp_group=tp_group, kv_dtype=kv_cache,
@@ -377,8 +381,10 @@ def parse_args(argv=None):
     ap.add_argument("--tokenizer", default=None)
     ap.add_argument("--api-key", default=os.environ.get("MXLLM_API_KEY"))
     ap.add_argument("--served-name", default=None)
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default=os.environ.get("MXLLM_ENGINE_WEIGHTS", "bf16"),
-                    help="fp8: e4m3 projection weights (serving quantisation, mxllm/serve/quant.py)")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"],
+                    default=os.environ.get("MXLLM_ENGINE_WEIGHTS", "bf16"),
+                    help="fp8: e4m3 projection weights; mxfp4: OCP MXFP4 projection weights, e2m1 codes with one "
+                         "e8m0 scale per 32 (serving quantisation, mxllm/serve/quant.py)")
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree: launch with torchrun --nproc-per-node=TP; rank 0 serves HTTP, "
                          "the other ranks follow its schedule")
