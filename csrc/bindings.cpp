@@ -472,8 +472,11 @@ at::Tensor swiglu_lora(const c10::optional<at::Tensor>& dm, const at::Tensor& gu
   const int64_t ldv = check_rows_bf16(v, "v");
   DevGuard g(gu.device());
   const bool bwd = dm.has_value();
-  const int64_t F2 = gu.size(-1), F = F2 / 2, T = gu.numel() / F2;
-  MX_CHECK(gu.dim() == 2 && F % 128 == 0 && T % 16 == 0, "swiglu_lora: [T, 2F] with T % 16 == 0, F % 128 == 0");
+  // the width first: F = F2 / 2 would take an odd F2 (rows then read with the wrong stride), and T divides by it
+  MX_CHECK(gu.dim() == 2 && gu.size(1) > 0 && gu.size(1) % 256 == 0,
+           "swiglu_lora: gu [T, 2F] with F % 128 == 0 (gate | up halves of equal width)");
+  const int64_t F2 = gu.size(1), F = F2 / 2, T = gu.size(0);
+  MX_CHECK(T % 16 == 0, "swiglu_lora: [T, 2F] with T % 16 == 0");
   MX_CHECK(nrb >= 1 && nrb <= 4 && pad >= 16 * nrb && pad % 8 == 0, "swiglu_lora: 16 nrb <= pad");
   MX_CHECK(v.size(0) >= 16 * nrb && v.size(1) == (bwd ? F2 : F), "swiglu_lora: v shape");
   if (bwd) {
@@ -1659,9 +1662,17 @@ void lora_grads(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& g, 
   std::vector<int64_t> desc;
   auto add = [&](const uint16_t* X, int64_t lx, const uint16_t* G, int64_t lg, int64_t gw, uint16_t* out, int64_t os_n,
                  int64_t os_j, int64_t Nx, int64_t jb0, int64_t JB) {
-    // JB > 1 reads a 64-column G window starting at column 16 jb0
-    MX_CHECK(JB == 1 || 16 * jb0 + 64 <= gw, "lora_grads: operand tail too narrow");
+    MX_CHECK(16 * (jb0 + JB) <= gw, "lora_grads: operand tail too narrow");
     MX_CHECK(Nx % 64 == 0, "lora_grads: split sizes must be multiples of 64");
+    // JB > 1 reads a 64-column G window starting at column 16 jb0.  Where that window would run past the
+    // tail (two splits of r = 32 in a 64-column pad: the second split's blocks are columns 32..63), the
+    // blocks go as JB problems of one block each: the one-block form reads its 16 columns only
+    if (JB > 1 && 16 * jb0 + 64 > gw) {
+      for (int64_t j = 0; j < JB; ++j)
+        desc.insert(desc.end(), {(int64_t)X, (int64_t)G, (int64_t)(out + 16 * j * os_j), lx, lg, os_n, os_j, Nx,
+                                 jb0 + j, (int64_t)1});
+      return;
+    }
     desc.insert(desc.end(), {(int64_t)X, (int64_t)G, (int64_t)out, lx, lg, os_n, os_j, Nx, jb0, JB});
   };
   // dA: R columns of g in chunks of <= 4 blocks

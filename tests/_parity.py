@@ -108,6 +108,32 @@ W8_Y_MEASURED = (0.00388, 7.83e-07)
 W8_Y = (ULP_BF16, 1.57e-06)  # 2 x 0.00388 < one ulp; 2 x 7.83e-07
 W8_DEQ_Y_MEASURED = (0.00379, 2.6e-07)
 W8_DEQ_Y = (ULP_BF16, 5.2e-07)  # 2 x 0.00379 < one ulp; 2 x 2.6e-07
+# The LoRA training path (tests/test_lora_strict_gpu.py; ``python -m tests.test_lora_strict_gpu`` prints the
+# measurements, tests/_lora_cases.py ``measure`` makes them).  SWIGLU_LORA_TAIL: fp32
+# ``s * (out.float() @ V.float().t())`` against the fp64 product of the same bf16 ``out``, each row against
+# its maximum.  LORA_PROJ_*: the fp32 model of the augmented projection documented in mxllm/ops/linear.py
+# (_LoRAAugFn) against plain fp64 with no intermediate rounding; the abs terms are those of the two stored
+# bf16 tails t = s x A^T and g = s dy B, not of fp32 arithmetic.  LORA_MLP_*: the same models chained through
+# the SwiGLU, every tensor that crosses an op boundary (gu, m, dm, dgu) rounded to bf16 as the ops store
+# it.  Every output against its row's maximum: at these Gaussian operands none cancels as a whole.
+SWIGLU_LORA_TAIL_MEASURED = (0.00389, 9.47e-07)
+SWIGLU_LORA_TAIL = (ULP_BF16, 1.89e-06)  # 2 x 0.00389 < one ulp; 2 x 9.47e-07
+LORA_PROJ_Y_MEASURED = (0.00389, 0.00313)
+LORA_PROJ_Y = (ULP_BF16, 0.00626)  # 2 x 0.00389 < one ulp; 2 x 0.00313
+LORA_PROJ_DX_MEASURED = (0.00389, 0.00289)
+LORA_PROJ_DX = (ULP_BF16, 0.00578)  # 2 x 0.00389 < one ulp; 2 x 0.00289
+LORA_PROJ_DA_MEASURED = (0.00389, 0.00318)
+LORA_PROJ_DA = (ULP_BF16, 0.00636)  # 2 x 0.00389 < one ulp; 2 x 0.00318
+LORA_PROJ_DB_MEASURED = (0.00389, 0.0051)
+LORA_PROJ_DB = (ULP_BF16, 0.0102)  # 2 x 0.00389 < one ulp; 2 x 0.0051
+LORA_MLP_Y_MEASURED = (0.00389, 0.0109)
+LORA_MLP_Y = (ULP_BF16, 0.0218)  # 2 x 0.00389 < one ulp; 2 x 0.0109
+LORA_MLP_DX_MEASURED = (0.00389, 0.00819)
+LORA_MLP_DX = (ULP_BF16, 0.0164)  # 2 x 0.00389 < one ulp; 2 x 0.00819
+LORA_MLP_DA_MEASURED = (0.00388, 0.00751)
+LORA_MLP_DA = (ULP_BF16, 0.015)  # 2 x 0.00388 < one ulp; 2 x 0.00751
+LORA_MLP_DB_MEASURED = (0.00388, 0.0232)
+LORA_MLP_DB = (ULP_BF16, 0.0464)  # 2 x 0.00388 < one ulp; 2 x 0.0232
 
 
 def assert_exact(out: torch.Tensor, want: torch.Tensor, name: str = "") -> None:

@@ -69,6 +69,9 @@ def test_swiglu(gpu, T, F):
     assert torch.equal(dgu2, dgu) and torch.equal(m2, m)
 
 
+# The large shapes under one norm ratio.  The exact and per-element checks of this kernel -- every template
+# instantiation with several trips per workgroup and uneven splits, one-hot routing, the operand refusals --
+# are tests/test_lora_strict_gpu.py ``test_swiglu_lora_strict`` / ``test_swiglu_lora_refusals``.
 @pytest.mark.parametrize("rbw", ["1", "2", "4"])
 @pytest.mark.parametrize("bwd", [False, True])
 @pytest.mark.parametrize("T,F,R", [(16, 128, 16), (48, 384, 32), (1024, 1536, 48), (256, 256, 64), (4096, 28672, 16)])
