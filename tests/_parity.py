@@ -134,6 +134,106 @@ LORA_MLP_DA_MEASURED = (0.00388, 0.00751)
 LORA_MLP_DA = (ULP_BF16, 0.015)  # 2 x 0.00388 < one ulp; 2 x 0.00751
 LORA_MLP_DB_MEASURED = (0.00388, 0.0232)
 LORA_MLP_DB = (ULP_BF16, 0.0464)  # 2 x 0.00388 < one ulp; 2 x 0.0232
+# The transformer layer (tests/test_layer_strict_gpu.py; ``python -m tests.test_layer_strict_gpu`` prints the
+# measurements, tests/_layer_cases.py ``measure`` makes them): one ``Llama._layer`` call fed by its add_rms_norm,
+# the fp32 model of the layer with every tensor the ops store between kernels rounded to bf16 (listed in that
+# module's doc) against the exact fp64 function of the same bf16 inputs and its true gradients.  The abs terms
+# are those of the chain of bf16 intermediates, not of fp32 arithmetic.  Every output against its row's maximum
+# (a d-gamma: the vector's); max over both layers of every shape, and for the gradients over the targets
+# (returned to autograd, added to a preset buffer).  _F32: the gradients accumulated over two micro-batches
+# into an fp32 buffer (no output rounding: the rel term is fp32's).  LAYER_LORA_*: the LoRA layer, whose
+# stored tails add roundings; one DA / DB per projection, DB per diagonal block.
+# MODEL_*: the whole two-layer model on ids (embedding, first norm, both layers, fused head + cross-entropy with
+# bf16 logits and bf16 d(logits)), the same models chained, tied and untied head; per-layer gradients over both
+# layers.  MODEL_LOSS: the loss (fp32 output) against its own value; its measured abs term is three standard
+# errors of the mean of the per-token losses (rms of the model's per-token errors / sqrt(n_valid)), not one
+# draw of the mean's error: tests/_layer_cases.py ``measure_model`` says why.
+LAYER_DD_MEASURED = (0.00389, 0.00827)
+LAYER_DD = (ULP_BF16, 0.0165)  # 2 x 0.00389 < one ulp; 2 x 0.00827
+LAYER_DG_ATTN_MEASURED = (0.00385, 0.00852)
+LAYER_DG_ATTN = (ULP_BF16, 0.017)  # 2 x 0.00385 < one ulp; 2 x 0.00852
+LAYER_DG_ATTN_F32_MEASURED = (0, 0.00681)
+LAYER_DG_ATTN_F32 = (ULP_F32, 0.0136)  # 2 x 0 < one ulp; 2 x 0.00681
+LAYER_DG_MLP_MEASURED = (0.00384, 0.0077)
+LAYER_DG_MLP = (ULP_BF16, 0.0154)  # 2 x 0.00384 < one ulp; 2 x 0.0077
+LAYER_DG_MLP_F32_MEASURED = (0, 0.00593)
+LAYER_DG_MLP_F32 = (ULP_F32, 0.0119)  # 2 x 0 < one ulp; 2 x 0.00593
+LAYER_DG_NEXT_MEASURED = (0.00385, 0.00667)
+LAYER_DG_NEXT = (ULP_BF16, 0.0133)  # 2 x 0.00385 < one ulp; 2 x 0.00667
+LAYER_DG_NEXT_F32_MEASURED = (0, 0.0037)
+LAYER_DG_NEXT_F32 = (ULP_F32, 0.0074)  # 2 x 0 < one ulp; 2 x 0.0037
+LAYER_DW_D_MEASURED = (0.00389, 0.0102)
+LAYER_DW_D = (ULP_BF16, 0.0204)  # 2 x 0.00389 < one ulp; 2 x 0.0102
+LAYER_DW_D_F32_MEASURED = (0, 0.00926)
+LAYER_DW_D_F32 = (ULP_F32, 0.0185)  # 2 x 0 < one ulp; 2 x 0.00926
+LAYER_DW_GU_MEASURED = (0.00389, 0.0151)
+LAYER_DW_GU = (ULP_BF16, 0.0302)  # 2 x 0.00389 < one ulp; 2 x 0.0151
+LAYER_DW_GU_F32_MEASURED = (0, 0.0107)
+LAYER_DW_GU_F32 = (ULP_F32, 0.0214)  # 2 x 0 < one ulp; 2 x 0.0107
+LAYER_DW_O_MEASURED = (0.00389, 0.0135)
+LAYER_DW_O = (ULP_BF16, 0.027)  # 2 x 0.00389 < one ulp; 2 x 0.0135
+LAYER_DW_O_F32_MEASURED = (0, 0.0104)
+LAYER_DW_O_F32 = (ULP_F32, 0.0208)  # 2 x 0 < one ulp; 2 x 0.0104
+LAYER_DW_QKV_MEASURED = (0.00389, 0.0169)
+LAYER_DW_QKV = (ULP_BF16, 0.0338)  # 2 x 0.00389 < one ulp; 2 x 0.0169
+LAYER_DW_QKV_F32_MEASURED = (0, 0.0197)
+LAYER_DW_QKV_F32 = (ULP_F32, 0.0394)  # 2 x 0 < one ulp; 2 x 0.0197
+LAYER_H2_MEASURED = (0.00389, 0.00845)
+LAYER_H2 = (ULP_BF16, 0.0169)  # 2 x 0.00389 < one ulp; 2 x 0.00845
+LAYER_K_MEASURED = (0.00389, 0.0073)
+LAYER_K = (ULP_BF16, 0.0146)  # 2 x 0.00389 < one ulp; 2 x 0.0073
+LAYER_LORA_DA_D_MEASURED = (0.00389, 0.0188)
+LAYER_LORA_DA_D = (ULP_BF16, 0.0376)  # 2 x 0.00389 < one ulp; 2 x 0.0188
+LAYER_LORA_DA_GU_MEASURED = (0.00386, 0.0123)
+LAYER_LORA_DA_GU = (ULP_BF16, 0.0246)  # 2 x 0.00386 < one ulp; 2 x 0.0123
+LAYER_LORA_DA_O_MEASURED = (0.00388, 0.0153)
+LAYER_LORA_DA_O = (ULP_BF16, 0.0306)  # 2 x 0.00388 < one ulp; 2 x 0.0153
+LAYER_LORA_DA_QKV_MEASURED = (0.00389, 0.0194)
+LAYER_LORA_DA_QKV = (ULP_BF16, 0.0388)  # 2 x 0.00389 < one ulp; 2 x 0.0194
+LAYER_LORA_DB_D_MEASURED = (0.00387, 0.0272)
+LAYER_LORA_DB_D = (ULP_BF16, 0.0544)  # 2 x 0.00387 < one ulp; 2 x 0.0272
+LAYER_LORA_DB_GU_MEASURED = (0.00389, 0.0321)
+LAYER_LORA_DB_GU = (ULP_BF16, 0.0642)  # 2 x 0.00389 < one ulp; 2 x 0.0321
+LAYER_LORA_DB_O_MEASURED = (0.00388, 0.0282)
+LAYER_LORA_DB_O = (ULP_BF16, 0.0564)  # 2 x 0.00388 < one ulp; 2 x 0.0282
+LAYER_LORA_DB_QKV_MEASURED = (0.00389, 0.0369)
+LAYER_LORA_DB_QKV = (ULP_BF16, 0.0738)  # 2 x 0.00389 < one ulp; 2 x 0.0369
+LAYER_LORA_DD_MEASURED = (0.00389, 0.0322)
+LAYER_LORA_DD = (ULP_BF16, 0.0644)  # 2 x 0.00389 < one ulp; 2 x 0.0322
+LAYER_LORA_H2_MEASURED = (0.00389, 0.0146)
+LAYER_LORA_H2 = (ULP_BF16, 0.0292)  # 2 x 0.00389 < one ulp; 2 x 0.0146
+LAYER_LORA_K_MEASURED = (0.00389, 0.00651)
+LAYER_LORA_K = (ULP_BF16, 0.013)  # 2 x 0.00389 < one ulp; 2 x 0.00651
+LAYER_LORA_Q_MEASURED = (0.00389, 0.0064)
+LAYER_LORA_Q = (ULP_BF16, 0.0128)  # 2 x 0.00389 < one ulp; 2 x 0.0064
+LAYER_LORA_X2_MEASURED = (0.00389, 0.0202)
+LAYER_LORA_X2 = (ULP_BF16, 0.0404)  # 2 x 0.00389 < one ulp; 2 x 0.0202
+LAYER_Q_MEASURED = (0.00389, 0.00839)
+LAYER_Q = (ULP_BF16, 0.0168)  # 2 x 0.00389 < one ulp; 2 x 0.00839
+LAYER_X2_MEASURED = (0.00389, 0.0116)
+LAYER_X2 = (ULP_BF16, 0.0232)  # 2 x 0.00389 < one ulp; 2 x 0.0116
+MODEL_DEMB_MEASURED = (0.00389, 0.0129)
+MODEL_DEMB = (ULP_BF16, 0.0258)  # 2 x 0.00389 < one ulp; 2 x 0.0129
+MODEL_DEMB_TIED_MEASURED = (0.00389, 0.0322)
+MODEL_DEMB_TIED = (ULP_BF16, 0.0644)  # 2 x 0.00389 < one ulp; 2 x 0.0322
+MODEL_DG_ATTN_MEASURED = (0.00387, 0.0118)
+MODEL_DG_ATTN = (ULP_BF16, 0.0236)  # 2 x 0.00387 < one ulp; 2 x 0.0118
+MODEL_DG_FINAL_MEASURED = (0.00382, 0.00354)
+MODEL_DG_FINAL = (ULP_BF16, 0.00708)  # 2 x 0.00382 < one ulp; 2 x 0.00354
+MODEL_DG_MLP_MEASURED = (0.00382, 0.00633)
+MODEL_DG_MLP = (ULP_BF16, 0.0127)  # 2 x 0.00382 < one ulp; 2 x 0.00633
+MODEL_DHEAD_MEASURED = (0.00389, 0.0323)
+MODEL_DHEAD = (ULP_BF16, 0.0646)  # 2 x 0.00389 < one ulp; 2 x 0.0323
+MODEL_DW_D_MEASURED = (0.00389, 0.0392)
+MODEL_DW_D = (ULP_BF16, 0.0784)  # 2 x 0.00389 < one ulp; 2 x 0.0392
+MODEL_DW_GU_MEASURED = (0.00389, 0.0704)
+MODEL_DW_GU = (ULP_BF16, 0.141)  # 2 x 0.00389 < one ulp; 2 x 0.0704
+MODEL_DW_O_MEASURED = (0.00389, 0.0566)
+MODEL_DW_O = (ULP_BF16, 0.113)  # 2 x 0.00389 < one ulp; 2 x 0.0566
+MODEL_DW_QKV_MEASURED = (0.00389, 0.06)
+MODEL_DW_QKV = (ULP_BF16, 0.12)  # 2 x 0.00389 < one ulp; 2 x 0.06
+MODEL_LOSS_MEASURED = (0, 0.000162)
+MODEL_LOSS = (ULP_F32, 0.000324)  # 2 x 0 < one ulp; 2 x 0.000162
 
 
 def assert_exact(out: torch.Tensor, want: torch.Tensor, name: str = "") -> None:
