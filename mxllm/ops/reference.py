@@ -84,7 +84,10 @@ def swiglu(gate_up: torch.Tensor) -> torch.Tensor:
 
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
-    return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction="mean")
+    """Mean over the valid tokens; no valid token: loss 0 and a zero gradient (the kernels' and the chunked
+    path's clamped count), not the 0 / 0 of ``reduction="mean"``."""
+    n = (labels != ignore_index).sum().clamp(min=1)
+    return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction="sum") / n
 
 
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, lr: float, beta1: float,

@@ -53,7 +53,10 @@ gradient-ready notifications of every backward to what their owners rely on.
 Routes (``ROUTES``): the switches of mxllm/models/llama.py and mxllm/ops that select one of the three q/k/v and
 five MLP routes of ``Llama._layer``; ``apply_route`` sets them and installs the spies, ``check_route_ran`` holds
 the spies' record to what the route must have run.  The last section chains the same formula into the whole
-two-layer model (embedding, first norm, fused head + cross-entropy) for ``check_whole_model``.
+two-layer model (embedding, first norm, fused head + cross-entropy) for ``check_whole_model``; ``model_math`` takes
+the parameter values and the batch as arguments (``model_params`` / ``model_inputs`` give those of the tests; with
+``lora`` the LoRA layers chained the same way, the adapters alone trainable), which is what the reference of a
+training step (tests/_step_cases.py) evaluates at the parameters a trainer holds.
 """
 from __future__ import annotations
 
@@ -241,14 +244,15 @@ def _layer_body(c, W, x, h0, dt, r, model, defect=None, keep=lambda name, t: t):
         return y
 
     qkv = r(keep("qkv", proj("wqkv", x)))
-    pos = torch.arange(T) % c.S if defect != "rope-runs-on" else torch.arange(T)
-    cos, sin = [t[pos].to(dt)[:, None, :] for t in rope_tables(c)]
+    dev = x.device
+    pos = (torch.arange(T) % c.S if defect != "rope-runs-on" else torch.arange(T)).to(dev)
+    cos, sin = [t.to(dev)[pos].to(dt)[:, None, :] for t in rope_tables(c)]
     q3, k3, v3 = (qkv[:, :Hq * D].view(T, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D),
                   qkv[:, (Hq + Hkv) * D:].view(T, Hkv, D))
     heads = lambda t: t.view(c.B, c.S, -1, D).transpose(1, 2)  # noqa: E731
     q_pre, k_pre = heads(_rope(q3, cos, sin)), heads(_rope(k3, cos, sin))
     qh, kh, vh = r(q_pre, bwd=False), r(k_pre, bwd=False), heads(v3)
-    ii, jj = torch.arange(c.S).view(-1, 1), torch.arange(c.S).view(1, -1)
+    ii, jj = torch.arange(c.S, device=dev).view(-1, 1), torch.arange(c.S, device=dev).view(1, -1)
     vis = jj <= ii + (1 if defect == "mask-off-by-one" else 0)
     scale = 1.0 / math.sqrt(D)
     oh = _AttnModel.apply(qh, kh, vh, vis, scale) if model else _attn_exact(qh, kh, vh, vis, scale)
@@ -754,7 +758,7 @@ class _CEModel(torch.autograd.Function):
         losses = torch.logsumexp(lg, -1) - lg.gather(1, lab[:, None]).squeeze(1)
         g = torch.softmax(lg, -1)
         g[torch.arange(g.shape[0]), lab] -= 1.0
-        ctx.save_for_backward(x, w, (g * valid[:, None] / n).to(BF16).to(x.dtype))
+        ctx.save_for_backward(x, w, (g * valid[:, None] / n).to(BF16).to(x.dtype))  # (n > 0: model_math)
         return (losses * valid).sum() / n
 
     @staticmethod
@@ -763,19 +767,60 @@ class _CEModel(torch.autograd.Function):
         return (g @ w) * gl, (g.t() @ x) * gl, None
 
 
-def model_math(tied, dt, model, defect=None):
-    """The whole network in ``dt``: {loss [1], demb, dhead (untied), l<i>.<key>, dg_final}, before the output
-    rounding.  ``defect``: "tied-embedding-use-dropped", "ignored-labels-counted", "n-valid-plus-two", "ckpt-layer-dw-missing" /
-    "ckpt-layer-dw-doubled" (the gradients of layer 0's parameters -- the layer every checkpoint setting wraps --
-    not written, or written by both of its forward runs) (tests/test_layer_cases.py)."""
-    c, cfg = MODEL_CASE, config(MODEL_CASE)
-    ids, labels, emb, head = model_inputs(tied)
-    ids, labels = ids.reshape(-1), labels.reshape(-1)
+def model_params(tied, lora=0):
+    """{name: bf16 value} of the whole model of the tests, named as ``Llama.named_parameters`` names them:
+    ``layer_weights`` of the full case (``lora``: of LORA_256, adapters included) and the embedding / head of
+    ``model_inputs``."""
+    c = LORA_256 if lora else MODEL_CASE
+    assert lora in (0, LORA_256.lora)
+    _, _, emb, head = model_inputs(tied)
     ws = layer_weights(c)
-    L = [{k: v.to(dt).requires_grad_(True) for k, v in w.items()} for w in ws[:2]]
-    final = ws[2].to(dt).requires_grad_(True)
-    E = emb.to(dt).requires_grad_(True)
-    Wh = E if tied else head.to(dt).requires_grad_(True)
+    out = {"tok_emb": emb}
+    for i in (0, 1):
+        out[f"layers.{i}.attn_norm"], out[f"layers.{i}.mlp_norm"] = ws[i]["attn_norm"], ws[i]["mlp_norm"]
+        for p in PROJS:
+            out[f"layers.{i}.{p}.weight"] = ws[i][p]
+            if lora:
+                out[f"layers.{i}.{p}.lora_a"], out[f"layers.{i}.{p}.lora_b"] = ws[i][p + "_a"], ws[i][p + "_b"]
+    out["final_norm"] = ws[2]
+    if not tied:
+        out["lm_head"] = head
+    return out
+
+
+def param_key(name):
+    """The key of ``model_math``'s gradient of the parameter ``name``."""
+    if name in ("tok_emb", "lm_head", "final_norm"):
+        return {"tok_emb": "demb", "lm_head": "dhead", "final_norm": "dg_final"}[name]
+    _, i, rest = name.split(".", 2)
+    if rest in ("attn_norm", "mlp_norm"):
+        return f"l{i}.dg_{rest[:-5]}"
+    proj, leaf = rest.split(".")
+    return f"l{i}.d{ {'weight': 'w', 'lora_a': 'a', 'lora_b': 'b'}[leaf]}_{proj[1:]}"
+
+
+def trainable(name, lora):
+    return name.endswith(("lora_a", "lora_b")) if lora else True
+
+
+def model_math(tied, dt, model, defect=None, *, params, batch, lora=0, loss_scale=1.0):
+    """The whole network in ``dt`` at the parameter values ``params`` ({name: tensor}, ``model_params`` names) on
+    the batch ``batch`` = (ids, labels), on the parameters' device: {loss [1], losses, and the gradient of
+    ``loss_scale`` x loss for every trainable parameter: demb, dhead (untied), l<i>.<key>, dg_final; ``lora``:
+    l<i>.da_<proj> / l<i>.db_<proj> alone, the off-diagonal blocks of B without a gradient}, before the
+    output rounding.  No valid label: loss 0, every gradient 0.  ``defect``: "tied-embedding-use-dropped",
+    "ignored-labels-counted", "n-valid-plus-two", "ckpt-layer-dw-missing" / "ckpt-layer-dw-doubled" (the
+    gradients of layer 0's parameters -- the layer every checkpoint setting wraps -- not written, or written
+    by both of its forward runs) (tests/test_layer_cases.py)."""
+    c = LORA_256 if lora else MODEL_CASE
+    cfg = config(c)
+    dev = params["tok_emb"].device
+    ids, labels = [t.to(dev).reshape(-1) for t in batch]
+    P_ = {k: v.detach().to(dt).requires_grad_(trainable(k, lora)) for k, v in params.items()}
+    L = [{k.split(".", 2)[2].replace(".weight", "").replace(".lora_", "_"): v for k, v in P_.items()
+          if k.startswith(f"layers.{i}.")} for i in (0, 1)]
+    final, E = P_["final_norm"], P_["tok_emb"]
+    Wh = E if tied else P_["lm_head"]
 
     def r(t, fwd=True, bwd=True):
         return _Rnd.apply(t, fwd, bwd) if model else t
@@ -789,25 +834,29 @@ def model_math(tied, dt, model, defect=None):
         t = _layer_body(c, W, x, h, dt, r, model)
         x, h = r(t["x2"]), t["h2"]
     wh = r(Wh, fwd=False) if tied else Wh
-    if model:
+    n_valid = int((labels != IGNORE).sum())
+    if n_valid == 0:
+        loss = (x @ wh.t()).sum() * 0.0
+    elif model:
         loss = _CEModel.apply(x, wh, labels)
     else:
         loss = F_.cross_entropy(x @ wh.t(), labels, ignore_index=IGNORE)
     if defect == "ignored-labels-counted":
-        loss = loss * float((labels != IGNORE).sum()) / labels.numel()
+        loss = loss * float(n_valid) / labels.numel()
     if defect == "n-valid-plus-two":
-        loss = loss * float((labels != IGNORE).sum()) / float((labels != IGNORE).sum() + 2)
-    loss.backward()
+        loss = loss * float(n_valid) / float(n_valid + 2)
+    if loss.requires_grad:
+        (loss * loss_scale).backward()
     with torch.no_grad():  # the per-token losses the mean is taken of: what MODEL_LOSS is measured on
         lg, valid = x @ wh.t(), labels != IGNORE
         lg = lg.to(BF16).to(dt) if model else lg
         losses = (torch.logsumexp(lg, -1) - lg.gather(1, labels.clamp(min=0)[:, None]).squeeze(1))[valid]
-    out = {"loss": loss.detach().reshape(1), "losses": losses, "demb": E.grad, "dg_final": final.grad}
-    if not tied:
-        out["dhead"] = Wh.grad
-    for i in (0, 1):
-        out.update({f"l{i}.{k}": L[i][{"dg_attn": "attn_norm", "dg_mlp": "mlp_norm"}.get(k, "w" + k[3:])].grad
-                    for k in MODEL_LAYER_KEYS})
+    out = {"loss": loss.detach().reshape(1), "losses": losses}
+    for name, v in P_.items():
+        if v.requires_grad:
+            out[param_key(name)] = v.grad if v.grad is not None else torch.zeros_like(v)
+    for k in [k for k in out if ".db_" in k]:  # B is block-diagonal: the other blocks have no gradient
+        out[k] = out[k] * LC.block_mask(proj_splits(cfg, "w" + k.split("_")[1]), c.lora).to(dev)
     if defect in ("ckpt-layer-dw-missing", "ckpt-layer-dw-doubled"):
         f = 0.0 if defect.endswith("missing") else 2.0
         out.update({k: v * f for k, v in out.items() if k.startswith("l0.")})
@@ -816,12 +865,12 @@ def model_math(tied, dt, model, defect=None):
 
 @functools.lru_cache(maxsize=None)
 def model_ref64(tied):
-    return model_math(tied, F64, False)
+    return model_math(tied, F64, False, params=model_params(tied), batch=model_inputs(tied)[:2])
 
 
 @functools.lru_cache(maxsize=None)
 def model_model32(tied, defect=None):
-    return model_math(tied, F32, True, defect)
+    return model_math(tied, F32, True, defect, params=model_params(tied), batch=model_inputs(tied)[:2])
 
 
 F32_OUTPUTS = ("MODEL_LOSS",)  # the constants whose output dtype is fp32 whatever the gradient target

@@ -234,6 +234,114 @@ MODEL_DW_QKV_MEASURED = (0.00389, 0.06)
 MODEL_DW_QKV = (ULP_BF16, 0.12)  # 2 x 0.00389 < one ulp; 2 x 0.06
 MODEL_LOSS_MEASURED = (0, 0.000162)
 MODEL_LOSS = (ULP_F32, 0.000324)  # 2 x 0 < one ulp; 2 x 0.000162
+# The training step (tests/test_step_strict_gpu.py, tests/test_step_cases.py; ``python -m tests._step_cases`` prints
+# the measurements, tests/_step_cases.py ``measure`` makes them): the fp32 model of three optimizer steps --
+# ``model_math(..., F32, model=True)`` per micro-batch, accumulation in the gradient buffer's dtype with one
+# rounding per added micro-batch (_F32: fp32 adds), ``reference.adamw_`` in fp32 with an fp32 clip norm -- against
+# the fp64 reference, along the fp64 reference trajectory of every case (three parameter sets each; the MODEL_*
+# constants were measured at the initial weights only).  Gradient constants per parameter kind, each row against
+# its maximum; a kind whose step measurement came out no larger than its MODEL_* constant has no STEP_* twin and
+# is held to the MODEL_* one (DEMB_TIED, DW_O).  STEP_Z3_*: the same kinds at the weights ZeRO-3 seeds for itself
+# (N(0, 0.02), every norm weight 1), where a row's gradient is noisier against its maximum; the trainer's
+# constants are not widened for them.  STEP_ADAMW_*: master, m, v after one step from the same state and buffer,
+# each slot against its maximum, the model evaluated at the clipped gscale and at gscale (1 +- 6 x 2^-24): the
+# coefficient is one number per step shared by every element, and six fp32 roundings lie between the gradient
+# and it.  STEP_LOSS: three standard errors of the mean of the micro-batch means (``measure_model``'s rule),
+# relative to the loss.
+STEP_ADAMW_M_MEASURED = (0, 7.27e-07)
+STEP_ADAMW_M = (ULP_F32, 1.45e-06)  # 2 x 0 < one ulp; 2 x 7.27e-07
+STEP_ADAMW_P_MEASURED = (0, 1.17e-07)
+STEP_ADAMW_P = (ULP_F32, 2.34e-07)  # 2 x 0 < one ulp; 2 x 1.17e-07
+STEP_ADAMW_V_MEASURED = (0, 1.07e-06)
+STEP_ADAMW_V = (ULP_F32, 2.14e-06)  # 2 x 0 < one ulp; 2 x 1.07e-06
+STEP_DEMB_MEASURED = (0.00389, 0.0214)
+STEP_DEMB = (ULP_BF16, 0.0428)  # 2 x 0.00389 < one ulp; 2 x 0.0214
+STEP_DEMB_F32_MEASURED = (0, 0.0261)
+STEP_DEMB_F32 = (ULP_F32, 0.0522)  # 2 x 0 < one ulp; 2 x 0.0261
+STEP_DG_ATTN_MEASURED = (0.00387, 0.0147)
+STEP_DG_ATTN = (ULP_BF16, 0.0294)  # 2 x 0.00387 < one ulp; 2 x 0.0147
+STEP_DG_ATTN_F32_MEASURED = (0, 0.0127)
+STEP_DG_ATTN_F32 = (ULP_F32, 0.0254)  # 2 x 0 < one ulp; 2 x 0.0127
+STEP_DG_FINAL_MEASURED = (0.00382, 0.00894)
+STEP_DG_FINAL = (ULP_BF16, 0.0179)  # 2 x 0.00382 < one ulp; 2 x 0.00894
+STEP_DG_FINAL_F32_MEASURED = (0, 0.00526)
+STEP_DG_FINAL_F32 = (ULP_F32, 0.0105)  # 2 x 0 < one ulp; 2 x 0.00526
+STEP_DG_MLP_MEASURED = (0.00389, 0.0108)
+STEP_DG_MLP = (ULP_BF16, 0.0216)  # 2 x 0.00389 < one ulp; 2 x 0.0108
+STEP_DG_MLP_F32_MEASURED = (0, 0.00691)
+STEP_DG_MLP_F32 = (ULP_F32, 0.0138)  # 2 x 0 < one ulp; 2 x 0.00691
+STEP_DHEAD_MEASURED = (0.00389, 0.0406)
+STEP_DHEAD = (ULP_BF16, 0.0812)  # 2 x 0.00389 < one ulp; 2 x 0.0406
+STEP_DHEAD_F32_MEASURED = (0, 0.0322)
+STEP_DHEAD_F32 = (ULP_F32, 0.0644)  # 2 x 0 < one ulp; 2 x 0.0322
+STEP_DW_D_MEASURED = (0.00389, 0.0522)
+STEP_DW_D = (ULP_BF16, 0.104)  # 2 x 0.00389 < one ulp; 2 x 0.0522
+STEP_DW_D_F32_MEASURED = (0, 0.0317)
+STEP_DW_D_F32 = (ULP_F32, 0.0634)  # 2 x 0 < one ulp; 2 x 0.0317
+STEP_DW_GU_MEASURED = (0.00389, 0.0808)
+STEP_DW_GU = (ULP_BF16, 0.162)  # 2 x 0.00389 < one ulp; 2 x 0.0808
+STEP_DW_GU_F32_MEASURED = (0, 0.0469)
+STEP_DW_GU_F32 = (ULP_F32, 0.0938)  # 2 x 0 < one ulp; 2 x 0.0469
+STEP_DW_O_F32_MEASURED = (0, 0.0463)
+STEP_DW_O_F32 = (ULP_F32, 0.0926)  # 2 x 0 < one ulp; 2 x 0.0463
+STEP_DW_QKV_MEASURED = (0.00389, 0.0621)
+STEP_DW_QKV = (ULP_BF16, 0.124)  # 2 x 0.00389 < one ulp; 2 x 0.0621
+STEP_DW_QKV_F32_MEASURED = (0, 0.0482)
+STEP_DW_QKV_F32 = (ULP_F32, 0.0964)  # 2 x 0 < one ulp; 2 x 0.0482
+STEP_LORA_DA_D_MEASURED = (0.00389, 0.0531)
+STEP_LORA_DA_D = (ULP_BF16, 0.106)  # 2 x 0.00389 < one ulp; 2 x 0.0531
+STEP_LORA_DA_GU_MEASURED = (0.00389, 0.0427)
+STEP_LORA_DA_GU = (ULP_BF16, 0.0854)  # 2 x 0.00389 < one ulp; 2 x 0.0427
+STEP_LORA_DA_O_MEASURED = (0.00388, 0.0381)
+STEP_LORA_DA_O = (ULP_BF16, 0.0762)  # 2 x 0.00388 < one ulp; 2 x 0.0381
+STEP_LORA_DA_QKV_MEASURED = (0.00389, 0.0613)
+STEP_LORA_DA_QKV = (ULP_BF16, 0.123)  # 2 x 0.00389 < one ulp; 2 x 0.0613
+STEP_LORA_DB_D_MEASURED = (0.00388, 0.061)
+STEP_LORA_DB_D = (ULP_BF16, 0.122)  # 2 x 0.00388 < one ulp; 2 x 0.061
+STEP_LORA_DB_GU_MEASURED = (0.00389, 0.107)
+STEP_LORA_DB_GU = (ULP_BF16, 0.214)  # 2 x 0.00389 < one ulp; 2 x 0.107
+STEP_LORA_DB_O_MEASURED = (0.00389, 0.0825)
+STEP_LORA_DB_O = (ULP_BF16, 0.165)  # 2 x 0.00389 < one ulp; 2 x 0.0825
+STEP_LORA_DB_QKV_MEASURED = (0.00389, 0.154)
+STEP_LORA_DB_QKV = (ULP_BF16, 0.308)  # 2 x 0.00389 < one ulp; 2 x 0.154
+STEP_LOSS_MEASURED = (0, 0.0004)
+STEP_LOSS = (ULP_F32, 0.0008)  # 2 x 0 < one ulp; 2 x 0.0004
+STEP_Z3_DEMB_MEASURED = (0.00389, 0.0107)
+STEP_Z3_DEMB = (ULP_BF16, 0.0214)  # 2 x 0.00389 < one ulp; 2 x 0.0107
+STEP_Z3_DEMB_F32_MEASURED = (0, 0.0113)
+STEP_Z3_DEMB_F32 = (ULP_F32, 0.0226)  # 2 x 0 < one ulp; 2 x 0.0113
+STEP_Z3_DG_ATTN_MEASURED = (0.00389, 0.00679)
+STEP_Z3_DG_ATTN = (ULP_BF16, 0.0136)  # 2 x 0.00389 < one ulp; 2 x 0.00679
+STEP_Z3_DG_ATTN_F32_MEASURED = (0, 0.00711)
+STEP_Z3_DG_ATTN_F32 = (ULP_F32, 0.0142)  # 2 x 0 < one ulp; 2 x 0.00711
+STEP_Z3_DG_FINAL_MEASURED = (0.00389, 0.00621)
+STEP_Z3_DG_FINAL = (ULP_BF16, 0.0124)  # 2 x 0.00389 < one ulp; 2 x 0.00621
+STEP_Z3_DG_FINAL_F32_MEASURED = (0, 0.00577)
+STEP_Z3_DG_FINAL_F32 = (ULP_F32, 0.0115)  # 2 x 0 < one ulp; 2 x 0.00577
+STEP_Z3_DG_MLP_MEASURED = (0.00389, 0.00927)
+STEP_Z3_DG_MLP = (ULP_BF16, 0.0185)  # 2 x 0.00389 < one ulp; 2 x 0.00927
+STEP_Z3_DG_MLP_F32_MEASURED = (0, 0.01)
+STEP_Z3_DG_MLP_F32 = (ULP_F32, 0.02)  # 2 x 0 < one ulp; 2 x 0.01
+STEP_Z3_DHEAD_MEASURED = (0.00389, 0.057)
+STEP_Z3_DHEAD = (ULP_BF16, 0.114)  # 2 x 0.00389 < one ulp; 2 x 0.057
+STEP_Z3_DHEAD_F32_MEASURED = (0, 0.0593)
+STEP_Z3_DHEAD_F32 = (ULP_F32, 0.119)  # 2 x 0 < one ulp; 2 x 0.0593
+STEP_Z3_DW_D_MEASURED = (0.00389, 0.0718)
+STEP_Z3_DW_D = (ULP_BF16, 0.144)  # 2 x 0.00389 < one ulp; 2 x 0.0718
+STEP_Z3_DW_D_F32_MEASURED = (0, 0.0681)
+STEP_Z3_DW_D_F32 = (ULP_F32, 0.136)  # 2 x 0 < one ulp; 2 x 0.0681
+STEP_Z3_DW_GU_MEASURED = (0.00389, 0.153)
+STEP_Z3_DW_GU = (ULP_BF16, 0.306)  # 2 x 0.00389 < one ulp; 2 x 0.153
+STEP_Z3_DW_GU_F32_MEASURED = (0, 0.206)
+STEP_Z3_DW_GU_F32 = (ULP_F32, 0.412)  # 2 x 0 < one ulp; 2 x 0.206
+STEP_Z3_DW_O_MEASURED = (0.00389, 0.0732)
+STEP_Z3_DW_O = (ULP_BF16, 0.146)  # 2 x 0.00389 < one ulp; 2 x 0.0732
+STEP_Z3_DW_O_F32_MEASURED = (0, 0.0729)
+STEP_Z3_DW_O_F32 = (ULP_F32, 0.146)  # 2 x 0 < one ulp; 2 x 0.0729
+STEP_Z3_DW_QKV_MEASURED = (0.00389, 0.117)
+STEP_Z3_DW_QKV = (ULP_BF16, 0.234)  # 2 x 0.00389 < one ulp; 2 x 0.117
+STEP_Z3_DW_QKV_F32_MEASURED = (0, 0.406)
+STEP_Z3_DW_QKV_F32 = (ULP_F32, 0.812)  # 2 x 0 < one ulp; 2 x 0.406
 
 
 def assert_exact(out: torch.Tensor, want: torch.Tensor, name: str = "") -> None:
