@@ -95,7 +95,7 @@ int main(int argc, char** argv) {
     int bits = 0;
     for (auto w : mask) bits += __builtin_popcount(w);
     hipStream_t s;
-    CK(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size() * 32, mask.data()));
+    CK(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));  // size in 32-bit words
     where_kernel<<<nwg, 64, 0, s>>>(rec);
     CK(hipStreamSynchronize(s));
     CK(hipMemcpy(host.data(), rec, host.size() * 4, hipMemcpyDeviceToHost));

@@ -376,7 +376,9 @@ int64_t cu_masked_stream(int64_t device, std::vector<int64_t> mask) {
   std::vector<uint32_t> w(mask.size());
   for (size_t i = 0; i < mask.size(); ++i) w[i] = (uint32_t)(mask[i] & 0xffffffffLL);
   hipStream_t s = nullptr;
-  hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)(w.size() * 32), w.data());
+  // the size is the number of 32-bit words of the mask, not of bits: the runtime reads that many words
+  hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)w.size(), w.data());
+  if (e != hipSuccess) (void)hipGetLastError();  // reported here: not left for the next launch to report
   MX_CHECK(e == hipSuccess, "hipExtStreamCreateWithCUMask: ", hipGetErrorString(e));
   return (int64_t)reinterpret_cast<intptr_t>(s);
 }
