@@ -5,10 +5,13 @@ call) beside ``w8_linear`` and the bf16 skinny GEMM on the same shapes; variants
 process (median of per-call events, median over rounds).  Every variant cycles through enough copies of
 its weight to exceed the 256 MB Infinity Cache, so each call streams from HBM as a decode step does.
 
-``--crossover``: the pass route of ``w4_linear`` (one weight pass per 32 rows) against dequantise + bf16
-GEMM at M = 32 .. 256: where MXLLM_W4_STREAM_M's default comes from.
+The ``tile`` column is the LDS-tiled kernel (``w4_gemm``, w4a16_tile_kernel) on the same call.
 
-Usage: python bench/w4_probe.py [--ms 1,4,8,16,32] [--nc 0,1,2,4] [--rounds 5] [--crossover]
+``--crossover``: the pass route of ``w4_linear`` (one weight pass per 32 rows) against dequantise + bf16
+GEMM and against ``w4_gemm`` at M = 32 .. 256: where the defaults of MXLLM_W4_STREAM_M and
+MXLLM_W4_TILE_MAX_M come from.
+
+Usage: python bench/w4_probe.py [--ms 1,4,8,16,32] [--nc 0,1,2,4] [--rounds 5] [--crossover [--cross-ms 64,128]]
 """
 from __future__ import annotations
 
@@ -67,13 +70,16 @@ def probe(a, ops, dev):
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
             ref = (x @ wd.t()).float()
             res = {f"nc{nc}": [] for nc in a.nc.split(",")}
-            res.update(w8=[], bf16=[])
+            res.update(tile=[], w8=[], bf16=[])
             for _ in range(a.rounds):
                 for key in res:
                     if key.startswith("nc"):
                         os.environ["MXLLM_W4_NC"] = key[2:] if key != "nc0" else ""
                         close(ops.w4_linear(x, codes, scales, big), ref, (name, M, key))
                         res[key].append(time_us(lambda: ops.w4_linear(x, *next(w4), big), a.calls))
+                    elif key == "tile":
+                        close(ops.w4_gemm(x, codes, scales), ref, (name, M, key))
+                        res[key].append(time_us(lambda: ops.w4_gemm(x, *next(w4)), a.calls))
                     elif key == "w8":
                         res[key].append(time_us(lambda: ops.w8_linear(x, *next(w8)), a.calls))
                     else:
@@ -82,7 +88,7 @@ def probe(a, ops, dev):
             rec = {"case": f"{name} M{M} N{N} K{K}", "w4_mb": round(N * K * (0.5 + 1 / 32) / 1e6, 1)}
             for key, v in res.items():
                 us = statistics.median(v)
-                nbytes = N * K * (0.5 + 1 / 32 if key.startswith("nc") else 1 if key == "w8" else 2)
+                nbytes = N * K * (0.5 + 1 / 32 if key.startswith("nc") or key == "tile" else 1 if key == "w8" else 2)
                 rec[key] = {"us": round(us, 1), "tbps": round(nbytes / (us * 1e-6) / 1e12, 2)}
             print(json.dumps(rec), flush=True)
             out.append(rec)
@@ -98,14 +104,16 @@ def crossover(a, ops, dev):
         codes, scales = quantize_mxfp4((torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16))
         w4 = ring((codes, scales))
         wd = ops.w4_dequant(codes, scales)
-        for M in (32, 64, 128, 256):
+        for M in map(int, a.cross_ms.split(",")):
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
             ref = (x @ wd.t()).float()
             close(ops.w4_linear(x, codes, scales, big), ref, (name, M, "passes"))
             close(ops.w4_linear(x, codes, scales, 0) if M > 32 else x @ ops.w4_dequant(codes, scales).t(), ref,
                   (name, M, "dequant + gemm"))
-            res = {"passes": [], "dequant_gemm": []}
+            close(ops.w4_gemm(x, codes, scales), ref, (name, M, "tile"))
+            res = {"passes": [], "dequant_gemm": [], "tile": []}
             for _ in range(a.rounds):
+                res["tile"].append(time_us(lambda: ops.w4_gemm(x, *next(w4)), a.calls))
                 res["passes"].append(time_us(lambda: ops.w4_linear(x, *next(w4), big), a.calls))
                 res["dequant_gemm"].append(time_us(lambda: x @ ops.w4_dequant(*next(w4)).t(), a.calls))
             rec = {"case": f"{name} M{M} N{N} K{K}"}
@@ -124,6 +132,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--cross-ms", default="32,64,128,256", help="row counts of the --crossover table")
     ap.add_argument("--json-out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)

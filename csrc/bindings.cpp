@@ -1630,6 +1630,33 @@ at::Tensor w4_linear(const at::Tensor& x, const at::Tensor& codes, const at::Ten
   return at::mm(x, w.t());
 }
 
+// y[M, N] = x[M, K] . dequant(codes, scales)^T on the LDS-tiled kernel (mxfp4_gemm.hip w4a16_tile_kernel):
+// the 4-bit weights are streamed once whatever M is.  No other route: a call the kernel does not take
+// raises.  The f32 workspace of a K-split launch comes from the caching allocator, so the op can be
+// captured into a hipGraph like w4_linear.
+at::Tensor w4_gemm(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales) {
+  sk_rows("w4_gemm", "x", x, x.device());
+  w4_weights("w4_gemm", codes, scales, x.device());
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  MX_CHECK(2 * codes.size(1) == K, "w4_gemm: x has ", K, " columns, the codes ", 2 * codes.size(1));
+  DevGuard g(x.device());
+  auto y = at::empty({M, N}, x.options());
+  if (M == 0 || N == 0) return y;
+  const int64_t ldx = M <= 1 ? K : x.stride(0);  // the stride of a one-row view is arbitrary
+  const int parts = mx::w4t_splits(M, N, K);
+  at::Tensor ws;
+  if (parts > 1) ws = at::empty({parts, M, N}, x.options().dtype(at::kFloat));
+  mx::W4TileLaunch L{};
+  L.x = x.data_ptr(), L.ldx = ldx, L.codes = codes.data_ptr(), L.scales = scales.data_ptr();
+  L.y = y.data_ptr(), L.ldy = N, L.ws = parts > 1 ? ws.data_ptr() : nullptr;
+  L.M = M, L.N = N, L.K = K;
+  const int rc = mx_w4a16_tile(L, cur_stream());
+  MX_CHECK(rc != -1, "w4_gemm: the kernel does not take this call (mx::w4t_takes, csrc/kernels/w4_tile_args.h): M ", M,
+           ", N ", N, ", K ", K, ", row stride x ", ldx);
+  TORCH_CHECK(rc == 0, "mxllm kernel launch failed (w4_gemm) rc=", rc, " ", hipGetErrorString((hipError_t)rc));
+  return y;
+}
+
 // ---------------------------------------------------------------- LoRA rank-r GEMMs
 // out[:, 0:Vrows] = alpha * x . v^T (x [M, K], v [Vrows, K] row views, Vrows % 64 == 0):
 // the forward s x A^T / backward s dy B products written into the augmented-GEMM tails.
@@ -1828,6 +1855,7 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("skinny_norm_linear(Tensor h, Tensor? delta, Tensor gamma, float eps, Tensor w, bool swiglu) -> (Tensor, Tensor)");
   m.def("w8_dequant(Tensor q, Tensor scale) -> Tensor");
   m.def("w4_linear(Tensor x, Tensor codes, Tensor scales, int stream_m) -> Tensor");
+  m.def("w4_gemm(Tensor x, Tensor codes, Tensor scales) -> Tensor");
   m.def("w4_dequant(Tensor codes, Tensor scales) -> Tensor");
   m.def("quant_rows_e4m3(Tensor x) -> (Tensor, Tensor)");
   m.def("lora_xwt(Tensor x, Tensor v, Tensor(a!) out, float alpha, int rows=0) -> ()");
@@ -1896,6 +1924,7 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("skinny_norm_linear", &skinny_norm_linear);
   m.impl("w8_dequant", &w8_dequant);
   m.impl("w4_linear", &w4_linear);
+  m.impl("w4_gemm", &w4_gemm);
   m.impl("w4_dequant", &w4_dequant);
   m.impl("quant_rows_e4m3", &quant_rows_e4m3);
   m.impl("lora_xwt", &lora_xwt);

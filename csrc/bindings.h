@@ -14,6 +14,7 @@
 #include "kernels/skinny_args.h"
 #include "kernels/verify_args.h"
 #include "kernels/w4_args.h"
+#include "kernels/w4_tile_args.h"
 
 extern "C" {
 // attn_bwd.hip (operand rules: mx::ab_takes, kernels/attn_args.h)
@@ -81,6 +82,8 @@ int mx_w8_dequant(const uint8_t* q, const float* scale, uint16_t* w, int64_t N, 
 
 // mxfp4_gemm.hip (operand rules of the GEMM: mx::w4_takes, kernels/w4_args.h)
 int mx_w4a16_gemm(const mx::W4Launch& L, hipStream_t stream);
+// the LDS-tiled GEMM for more than 32 rows (operand rules: mx::w4t_takes, kernels/w4_tile_args.h)
+int mx_w4a16_tile(const mx::W4TileLaunch& L, hipStream_t stream);
 int mx_w4_dequant(const uint8_t* codes, const uint8_t* scales, uint16_t* w, int64_t N, int64_t K, hipStream_t stream);
 
 // gemm8.hip (operand rules of every entry point: mx::g8_takes, kernels/gemm8_args.h)

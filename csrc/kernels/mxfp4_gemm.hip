@@ -3,6 +3,7 @@
 // output, f32 accumulation.  The decode step is bound by streaming every projection weight once;
 // 4-bit weights halve that traffic again against fp8_gemm.hip, on which this kernel is modelled.
 // Format and reference: mxllm/serve/quant.py.  Which launches are taken: mx::w4_takes (w4_args.h).
+// More than 32 rows: w4a16_tile_kernel further down (X through LDS; mx::w4t_takes, w4_tile_args.h).
 //
 // Structure (memory-bound; the MFMA is nearly free):
 //  * workgroup = NW waves (8, or 4 where K is no multiple of 1024) x 16 * NC output channels; the
@@ -191,6 +192,205 @@ static void w4_launch_nc(int nc, const W4Launch& L, hipStream_t stream) {
   else w4a16_gemm_kernel<MB, NW, 1><<<N / 16, 64 * NW, 0, stream>>>(x, L.ldx, q, s, y, L.ldy, M, N, K);
 }
 
+// ---------------------------------------------------------------- LDS-tiled kernel: more than 32 rows
+// The kernel above re-reads its X fragments from global memory in every wave: 2 M bytes per k against
+// 8 .. 32 weight bytes, which binds it at 32 rows.  Here a workgroup owns W4T_BN = 128 channels and ALL
+// rows of an M-block (16 * MB = 32 / 64 / 128; more rows over grid.y), and its four waves split the
+// CHANNELS (two 16-channel groups each), not K:
+//  * a weight byte is used by exactly one wave, so codes and scale words go from global memory straight
+//    into registers as above (16-B loads of one 32-k scale block, dequant8_fp4), one chunk ahead of the
+//    MFMAs that use them;
+//  * the X tile of a 128-k chunk ([16 MB rows][256 B]) is staged ONCE per workgroup by LDS-DMA
+//    (raw_ptr_buffer_load_lds, 16 B per lane, MB 1-KiB pieces per wave) into a two-slot ring: chunk
+//    c + 1 lands under the MFMAs of chunk c.  Every wave reads all of it as its MFMA B fragments:
+//    4 MB ds_read_b128 feed 8 MB MFMAs;
+//  * the buffer descriptor starts at the M-block's first row and holds num_records = (rows - 1) * ldx
+//    * 2 + K * 2 bytes, rows = min(16 MB, M - m0): a row at or past M starts at or past num_records
+//    (ldx >= K) and reads as zeros, the pad between two rows (k >= K) is never addressed;
+//  * swizzle: the 16-B chunk q of row r is stored at q ^ (r & 15), applied to each lane's SOURCE
+//    offset (the DMA writes lane-linearly).  A fragment read is 16 lanes x one chunk index x 16
+//    consecutive rows: 16 different slots, all 64 banks once;
+//  * k inside a chunk is permuted exactly as above on both sides: lane group g, MFMA step s take
+//    k = 32g + 8s + j, i.e. code word s of the lane's load and X chunk 4g + s;
+//  * narrow grids (mx::w4t_splits): grid.z K parts of whole chunks; a part stores its f32 sums to
+//    ws[z][m][n] and w4_tile_sum_kernel adds the parts in the order z = 0, 1, ...: no atomics, the
+//    result does not depend on the launch order.
+// LDS: 2 x MB x 4 KiB (64 KiB at 128 rows: two workgroups per CU).  The LDS reads are inline asm (hipcc's
+// waitcnt pass would drain the in-flight DMA and weight loads before a read it can see), waited by
+// counted lgkmcnt; a slot is refilled only after the barrier that follows its last read.
+template <int MB>
+__global__ void __launch_bounds__(64 * W4T_NW, 2)
+w4a16_tile_kernel(const uint16_t* __restrict__ X, int64_t ldx, const uint8_t* __restrict__ Q,
+                  const uint8_t* __restrict__ S, uint16_t* __restrict__ Y, int64_t ldy, float* __restrict__ WS, int M,
+                  int N, int K) {
+  constexpr int NC = W4T_NC, BM = 16 * MB, TILE = BM * 256;
+  __shared__ __attribute__((aligned(1024))) char smem[2 * TILE];
+  typedef __attribute__((address_space(3))) void* lptr_t;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * W4T_BN + w * 16 * NC;  // this wave's first channel
+  const int m0 = blockIdx.y * BM;
+  const int kq = K / (int)gridDim.z, kb = blockIdx.z * kq;  // this workgroup's K part
+  const int nch = kq / W4T_CHUNK;
+  // channel groups at or past N (N is whole groups, not whole workgroups) load channel N - 1 and store nothing
+  const uint8_t* qrow[NC];
+  const uint8_t* srow[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const int64_t n = min(n0 + 16 * j + c, N - 1);
+    qrow[j] = Q + n * (K / 2) + kb / 2 + 16 * g;
+    srow[j] = S + n * (K / 32) + kb / 32;
+  }
+  // LDS-DMA: piece p = w * MB + i is rows 4p .. 4p + 3 of the tile; lane l fills slot l & 15 of row 4p + (l >> 4)
+  const int rows = min(BM, M - m0);
+  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(X + (int64_t)m0 * ldx), 0, (int)((rows - 1) * ldx * 2 + (int64_t)K * 2), 0x00020000);
+  int voff[MB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    const int row = 4 * (w * MB + i) + g;
+    voff[i] = (int)(row * ldx * 2) + kb * 2 + 16 * (c ^ (row & 15));
+  }
+  auto dma = [&](int slot, int ch) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+      const int off = voff[i] + ch * 256;  // through a local: see prefill_paged.hip glds_piece
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lptr_t)(smem + slot * TILE + (w * MB + i) * 1024), 16, off, 0, 0,
+                                               0);
+    }
+  };
+  auto wload = [&](int ch, u32x4_w4 (&q)[NC], uint32_t (&sw)[NC]) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      q[j] = *reinterpret_cast<const u32x4_w4*>(qrow[j] + ch * 64);
+      sw[j] = *reinterpret_cast<const uint32_t*>(srow[j] + ch * 4);
+    }
+  };
+  // B fragment of token block mb, step s: row 16 mb + c (row & 15 == c), chunk 4g + s
+  const uint32_t lds0 = lds_addr(smem);
+  uint32_t ra[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) ra[s] = lds0 + c * 256 + 16 * ((4 * g + s) ^ c);
+
+  f32x4 acc[NC][MB];
+#pragma unroll
+  for (int j = 0; j < NC; ++j)
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) acc[j][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // one chunk out of ring slot SLOT: step s + 1's fragments are read under step s's MFMAs
+  auto compute = [&](auto slot_c, const u32x4_w4 (&q)[NC], const uint32_t (&sw)[NC]) {
+    constexpr int OFF = decltype(slot_c)::value * TILE;
+    float sc[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) sc[j] = e8m0_to_f32((sw[j] >> (8 * g)) & 0xFFu);
+    // unit u = (step s, HB token blocks): at most four fragments per unit keep 128 rows inside 256 VGPRs
+    constexpr int HB = MB < 4 ? MB : 4, NH = MB / HB, NU = 4 * NH;
+    u16x8 b[2][HB];
+    u16x8 a[NC];
+    auto rd = [&](int u, u16x8 (&x)[HB]) {
+#pragma unroll
+      for (int i = 0; i < HB; ++i) x[i] = rd128_off(ra[u / NH], OFF + ((u % NH) * HB + i) * 4096);
+    };
+    rd(0, b[0]);
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      if (u + 1 < NU) rd(u + 1, b[(u + 1) & 1]);
+      lds_wait_le(u + 1 < NU ? HB : 0);
+#pragma unroll
+      for (int i = 0; i < HB; ++i) pin(b[u & 1][i]);
+      if (u % NH == 0) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) a[j] = dequant8_fp4(q[j][u / NH], sc[j]);  // k = 32g + 8s + 0..7
+      }
+#pragma unroll
+      for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int i = 0; i < HB; ++i) {
+          f32x4& d = acc[j][(u % NH) * HB + i];
+          d = mfma16_w4(a[j], b[u & 1][i], d);
+        }
+    }
+  };
+  // the DMA of this wave landed, then every wave's; every wave's reads of the other slot are done
+  auto sync = [&]() {
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), visible to hipcc's waitcnt pass
+    __syncthreads();
+  };
+
+  u32x4_w4 q0[NC], q1[NC];
+  uint32_t sw0[NC], sw1[NC];
+  dma(0, 0);
+  wload(0, q0, sw0);
+  sync();
+  // chunk 0's weights are in registers HERE: sunk into the loop, their loads would be pending at the loop
+  // header and hipcc would wait vmcnt(0) there in every iteration, i.e. for the DMA issued just before
+#pragma unroll
+  for (int j = 0; j < NC; ++j) asm volatile("" : "+v"(q0[j]), "+v"(sw0[j]));
+  for (int ch = 0; ch < nch; ch += 2) {
+    if (ch + 1 < nch) {
+      dma(1, ch + 1);
+      wload(ch + 1, q1, sw1);
+    }
+    compute(std::integral_constant<int, 0>{}, q0, sw0);
+    sync();
+    if (ch + 1 >= nch) break;
+    if (ch + 2 < nch) {
+      dma(0, ch + 2);
+      wload(ch + 2, q0, sw0);
+    }
+    compute(std::integral_constant<int, 1>{}, q1, sw1);
+    sync();
+  }
+
+  // C[row = channel 4g + i][col = token c] per (group, token block)
+  const int64_t part = (int64_t)blockIdx.z * M;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const int n = n0 + 16 * j + 4 * g;
+    if (n0 + 16 * j >= N) continue;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+      const int m = m0 + mb * 16 + c;
+      if (m >= M) continue;
+      if (gridDim.z > 1) {
+        *reinterpret_cast<f32x4*>(WS + (part + m) * N + n) = acc[j][mb];
+      } else {
+        u16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = f2bf(acc[j][mb][i]);
+        *reinterpret_cast<u16x4*>(Y + (int64_t)m * ldy + n) = o;
+      }
+    }
+  }
+}
+
+// Y[m][n .. n + 3] = bf16(ws[0][m][n ..] + ws[1][m][n ..] + ...), the parts in that order
+__global__ void __launch_bounds__(256) w4_tile_sum_kernel(const float* __restrict__ WS, uint16_t* __restrict__ Y,
+                                                          int64_t ldy, int64_t M, int64_t N, int parts) {
+  const int64_t n4 = N / 4, total = M * n4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t m = i / n4, n = (i % n4) * 4;
+    f32x4 s = *reinterpret_cast<const f32x4*>(WS + m * N + n);
+    for (int p = 1; p < parts; ++p) s += *reinterpret_cast<const f32x4*>(WS + (p * M + m) * N + n);
+    u16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = f2bf(s[j]);
+    *reinterpret_cast<u16x4*>(Y + m * ldy + n) = o;
+  }
+}
+
+template <int MB>
+static void w4t_launch(const W4TileLaunch& L, int parts, hipStream_t stream) {
+  const dim3 grid((unsigned)((L.N + W4T_BN - 1) / W4T_BN), (unsigned)((L.M + 16 * MB - 1) / (16 * MB)),
+                  (unsigned)parts);
+  w4a16_tile_kernel<MB><<<grid, 64 * W4T_NW, 0, stream>>>(
+      static_cast<const uint16_t*>(L.x), L.ldx, static_cast<const uint8_t*>(L.codes),
+      static_cast<const uint8_t*>(L.scales), static_cast<uint16_t*>(L.y), L.ldy, static_cast<float*>(L.ws), (int)L.M,
+      (int)L.N, (int)L.K);
+}
+
 }  // namespace mx
 
 using namespace mx;
@@ -232,6 +432,25 @@ extern "C" int mx_w4a16_gemm(const W4Launch& L, hipStream_t stream) {
   } else {
     if (nw == 8) w4_launch_nc<2, 8>(nc, L, stream);
     else w4_launch_nc<2, 4>(nc, L, stream);
+  }
+  return (int)hipGetLastError();
+}
+
+// The LDS-tiled GEMM for any row count (operand rules: mx::w4t_takes, w4_tile_args.h).  L.ws holds
+// mx::w4t_splits(M, N, K) x M x N floats where that is above 1.
+extern "C" int mx_w4a16_tile(const W4TileLaunch& L, hipStream_t stream) {
+  if (L.M <= 0) return 0;
+  if (!w4t_takes(L)) return -1;
+  const int parts = w4t_splits(L.M, L.N, L.K);
+  switch (w4t_mblocks(L.M)) {
+    case 2: w4t_launch<2>(L, parts, stream); break;
+    case 4: w4t_launch<4>(L, parts, stream); break;
+    default: w4t_launch<8>(L, parts, stream); break;
+  }
+  if (parts > 1) {
+    const int grid = (int)std::min<int64_t>(4096, (L.M * (L.N / 4) + 255) / 256);
+    w4_tile_sum_kernel<<<grid, 256, 0, stream>>>(static_cast<const float*>(L.ws), static_cast<uint16_t*>(L.y), L.ldy,
+                                                 L.M, L.N, parts);
   }
   return (int)hipGetLastError();
 }

@@ -33,7 +33,11 @@ ARCH = os.environ.get("MXLLM_ARCH", "gfx950")
 
 
 # per-kernel-file compiler options (A/B experiments: MXLLM_FILE_FLAGS="file.hip=-opt1 -opt2;other.hip=...")
-PER_FILE_HIP_FLAGS: dict[str, list[str]] = {}
+# mxfp4_gemm.hip: no packed-f32 VALU forms (v_pk_add_f32 and kin) -- its f32x4 sums (the LDS reduction, the
+# K-split sum pass) are compiled to plain per-component adds
+PER_FILE_HIP_FLAGS: dict[str, list[str]] = {
+    "mxfp4_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 for _item in filter(None, os.environ.get("MXLLM_FILE_FLAGS", "").split(";")):
     _f, _, _opts = _item.partition("=")
     PER_FILE_HIP_FLAGS.setdefault(_f.strip(), []).extend(shlex.split(_opts))

@@ -153,9 +153,26 @@ MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 # instead.  The default is the largest M at which the passes still won on the Llama-3.1 70B projection
 # shapes (bench/w4_probe.py --crossover; table in profiles/mxfp4/README.md), passes / dequantise + GEMM in
 # us for the four projections of a layer: 32 rows 307 / 753, 64 rows 554 / 805 (qkv alone loses, 95 / 69),
-# 128 rows 1049 / 899, 256 rows 2046 / 1089.  Both routes are slower than the bf16 and fp8 engines at 64
-# rows (70B decode step 48.6 ms against 36.2 / 26.2 ms): the 32-row kernel is bound by its X traffic.
+# 128 rows 1049 / 899, 256 rows 2046 / 1089.  Both routes are bound well above the weight bytes (the 32-row
+# kernel by its X traffic), which is why 33 .. TILE_MAX_M rows go to w4_gemm below; these two remain for
+# TILE_MAX_M = 0, for more rows and for shapes w4_gemm does not take.
 STREAM_M = int(os.environ.get("MXLLM_W4_STREAM_M", "64"))
+
+# Calls of 33 .. TILE_MAX_M rows run on the LDS-tiled HIP kernel (w4_gemm, mxfp4_gemm.hip
+# w4a16_tile_kernel): it stages the X tile of a k-chunk in LDS once per workgroup, so the 4-bit weights are
+# streamed once whatever the row count.  0 switches the route off: w4_linear as above.  Up to 32 rows
+# always run on w4_linear.  The default is the largest measured M at which `tile` beat `dequant + GEMM` on
+# the 70B layer sum, table "LDS-tiled kernel" of profiles/mxfp4/README.md (bench/w4_probe.py --crossover),
+# passes / dequantise + GEMM / tile in us: 64 rows 525 / 862 / 246, 128 rows 987 / 956 / 311, 256 rows
+# 1939 / 1144 / 538, 512 rows 3826 / 1231 / 969, 1024 rows 7563 / 1765 / 1676 (the 8B shapes cross between
+# 512 and 1024: 457 against 444 at 1024).  More rows were not measured.
+TILE_MAX_M = int(os.environ.get("MXLLM_W4_TILE_MAX_M", "1024"))
+
+
+def _tile_takes(x2: torch.Tensor, N: int, K: int) -> bool:
+    """The rules of mx::w4t_takes (csrc/kernels/w4_tile_args.h) a W4Linear call can miss; w4_gemm raises on
+    the rest."""
+    return N % 16 == 0 and K % 512 == 0 and x2.data_ptr() % 16 == 0
 
 
 def quantize_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -216,6 +233,8 @@ class W4Linear(nn.Module):
             x2 = x2.contiguous()  # the HIP kernel takes 16-B-aligned rows
         if not use_native(x2):
             y = torch.matmul(x2, dequantize_mxfp4(self.codes, self.scales).to(x2.dtype).t())
+        elif 32 < x2.shape[0] <= TILE_MAX_M and _tile_takes(x2, self.out_features, self.in_features):
+            y = native().w4_gemm(x2, self.codes, self.scales)  # LDS-tiled HIP kernel: one weight pass
         else:
             # weight-streaming HIP kernel, one pass per 32 rows up to STREAM_M rows; beyond, and for
             # shapes it does not take, w4_linear dequantises to bf16 and runs hipBLASLt
