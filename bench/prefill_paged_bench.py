@@ -12,6 +12,11 @@
     ``prefill_chunk`` unset (prefix cache only), 2048 and 8192.  Time: host clock around steps that end in the
     sampler's read-back (a device synchronise).
 
+``--kv-cache fp8``: both parts over the fp8 (kv8) KV cache.  (a) times the kv8 kernel
+(``prefill_attn_paged_kv8``), the gather route that dequantises the gathered rows, and -- as ``bf16_hip`` -- the
+bf16 kernel over the dequantised pools, which computes the same bits: the ratio is the cost of the decode feed.
+(b) builds every engine with ``kv_dtype="fp8"``.
+
 One JSON line per measurement, then the box's calibration line (mxllm/utils/calibrate.py).
 
   python bench/prefill_paged_bench.py --part kernel,engine [--json-out out.jsonl]
@@ -44,6 +49,7 @@ def window(fn, n):
 def kernel_part(a, dev, emit):
     from mxllm.ops import native
     from mxllm.ops.decode import paged_attention_gather
+    from mxllm.serve.quant import kv8_dequantize
 
     ops = native()
     scale = 1.0 / math.sqrt(D)
@@ -64,7 +70,15 @@ def kernel_part(a, dev, emit):
         out_g = torch.empty_like(out_h)
         runs = {"hip": lambda: ops.prefill_attn_paged(q, kp, vp, bt, segs_t, scale, out_h),
                 "gather": lambda: paged_attention_gather(q, kp, vp, bt_host, segs, scale, out_g)}
-        if p0 == 0:
+        if a.kv_cache == "fp8":
+            (kq, ks), (vq, vs) = (ops.kv8_quant_rows(x.view(-1, D)) for x in (kp, vp))
+            kq, vq, ks, vs = kq.view(kp.shape), vq.view(vp.shape), ks.view(kp.shape[:3]), vs.view(vp.shape[:3])
+            kp, vp = kv8_dequantize(kq, ks), kv8_dequantize(vq, vs)  # the same values as a bf16 cache
+            out_b = torch.empty_like(out_h)
+            runs = {"hip": lambda: ops.prefill_attn_paged_kv8(q, kq, ks, vq, vs, bt, segs_t, scale, out_h),
+                    "gather": lambda: paged_attention_gather(q, kq, vq, bt_host, segs, scale, out_g, ks, vs),
+                    "bf16_hip": lambda: ops.prefill_attn_paged(q, kp, vp, bt, segs_t, scale, out_b)}
+        elif p0 == 0:
             qh = q.transpose(0, 1).contiguous().unsqueeze(0)
             kc = torch.randn(1, HKV, n, D, device=dev, dtype=torch.bfloat16)
             vc = torch.randn(1, HKV, n, D, device=dev, dtype=torch.bfloat16)
@@ -82,13 +96,17 @@ def kernel_part(a, dev, emit):
         # the two routes compute the same thing (same rounding points): compare at the size that is timed
         diff = (out_h.float() - out_g.float()).abs().max().item()
         flops = 4.0 * HQ * D * (n * p0 + n * (n + 1) / 2)
-        res = {"part": "kernel", "Hq": HQ, "Hkv": HKV, "D": D, "n": n, "p0": p0, "max_abs_diff_hip_gather": diff}
+        res = {"part": "kernel", "kv_cache": a.kv_cache, "Hq": HQ, "Hkv": HKV, "D": D, "n": n, "p0": p0,
+               "max_abs_diff_hip_gather": diff}
         for name in runs:
             ts = sorted(t[name][2])
             med = ts[len(ts) // 2]
             res[name] = {"us": round(med * 1e6, 1), "us_min": round(ts[0] * 1e6, 1), "us_max": round(ts[-1] * 1e6, 1),
                          "tflops": round(flops / med / 1e12, 1), "calls_per_window": t[name][1]}
         res["hip_over_gather"] = round(res["gather"]["us"] / res["hip"]["us"], 3)
+        if "bf16_hip" in runs:  # the same bits from both kernels; time of the kv8 kernel over the bf16 kernel's
+            res["bits_equal_hip_bf16_hip"] = bool(torch.equal(out_h.view(torch.int16), out_b.view(torch.int16)))
+            res["kv8_over_bf16_time"] = round(res["hip"]["us"] / res["bf16_hip"]["us"], 3)
         emit(res)
         del kp, vp, q
         torch.cuda.empty_cache()
@@ -109,7 +127,8 @@ def engine_part(a, dev, emit):
     # ---- TTFT: shared prefix + tail, miss against hit, against the options off
     pool = 16 * (a.prefix + a.tail + 64)
     for label, kw in (("options_off", {}), ("prefix_cache", dict(prefix_cache=True))):
-        eng = Engine(model, max_batch=2, max_seq=a.prefix + a.tail + 64, kv_pool_tokens=pool, eos_ids=(-1,), **kw)
+        eng = Engine(model, max_batch=2, max_seq=a.prefix + a.tail + 64, kv_pool_tokens=pool, eos_ids=(-1,),
+                     kv_dtype=a.kv_cache, **kw)
         eng.generate([prompt(a.prefix + a.tail)], max_new_tokens=2)  # warm up: kernels, workspaces, graphs
         first, second = [], []
         for _ in range(a.rounds):
@@ -117,7 +136,7 @@ def engine_part(a, dev, emit):
             for acc in (first, second):  # a new prefix, then the same prefix with another tail
                 r = eng.generate([pre + prompt(a.tail)], max_new_tokens=2, return_requests=True)[0]
                 acc.append((r.t_first - r.t_submit, r.cached_tokens))
-        res = {"part": "ttft", "engine": label, "model": a.model, "prefix": a.prefix, "tail": a.tail}
+        res = {"part": "ttft", "engine": label, "kv_cache": a.kv_cache, "model": a.model, "prefix": a.prefix, "tail": a.tail}
         for name, acc in (("first_request", first), ("same_prefix_again", second)):
             ts = sorted(x for x, _ in acc)
             res[name] = {"ttft_ms": round(statistics.median(ts) * 1e3, 2), "min": round(ts[0] * 1e3, 2),
@@ -133,7 +152,7 @@ def engine_part(a, dev, emit):
     for label, kw in (("options_off", {}), ("prefix_cache_chunk_unset", dict(prefix_cache=True)),
                       ("prefill_chunk_2048", dict(prefill_chunk=2048)), ("prefill_chunk_8192", dict(prefill_chunk=8192))):
         eng = Engine(model, max_batch=n_stream + 1, max_seq=max_seq, kv_pool_tokens=pool, prefill_tokens=long_n + 1,
-                     eos_ids=(-1,), **kw)
+                     eos_ids=(-1,), kv_dtype=a.kv_cache, **kw)
         sp = SamplingParams(max_new_tokens=600)
         streams = [eng.submit(prompt(128), sp) for _ in range(n_stream)]
         for _ in range(40):  # the streaming batch is running; decode graphs captured
@@ -152,7 +171,7 @@ def engine_part(a, dev, emit):
                 gaps.append(time.perf_counter() - t0)
             assert long.error is None and long.cached_tokens == 0, (long.error, long.cached_tokens)
             assert all(not r.done.is_set() for r in streams), "the streams must outlive the long prompt"
-        emit({"part": "inter_token_gap", "engine": label, "model": a.model, "streams": n_stream, "long_prompt": long_n,
+        emit({"part": "inter_token_gap", "engine": label, "kv_cache": a.kv_cache, "model": a.model, "streams": n_stream, "long_prompt": long_n,
               "decode_step_ms_before": round(statistics.median(quiet) * 1e3, 2),
               "largest_gap_ms": round(max(gaps) * 1e3, 1), "steps_while_admitted": len(gaps),
               "long_prompt_ttft_ms": round((long.t_first - long.t_submit) * 1e3, 1)})
@@ -167,6 +186,7 @@ def main():
     ap.add_argument("--p0", default="0,2048,8192,30720")
     ap.add_argument("--rounds", type=int, default=5, help="alternating timed windows per route / requests per TTFT case")
     ap.add_argument("--window-ms", type=float, default=200.0, help="target length of a timed window")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--model", default="llama3.1-8b")
     ap.add_argument("--prefix", type=int, default=2048)
     ap.add_argument("--tail", type=int, default=128)

@@ -977,6 +977,25 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at:
 }
 
 // ---------------------------------------------------------------- paged-KV prefill attention
+// The device copy of a pass's segment table [nseg, 4] followed by its work table [nwork, 2]
+// (mx::pp_fill_work), kept for the next call with the same segments (every layer of one prefill pass).
+static at::Tensor pp_device_tables(const mx::PpSeg* sp, int64_t nseg, int64_t nwork, const at::Device& dev) {
+  static std::mutex mu;
+  static std::vector<int32_t> host_key;
+  static at::Tensor dev_tab;
+  std::lock_guard<std::mutex> lk(mu);
+  std::vector<int32_t> key((size_t)(4 * nseg + 2 * nwork));
+  std::memcpy(key.data(), sp, sizeof(int32_t) * 4 * (size_t)nseg);
+  mx::pp_fill_work(sp, nseg, key.data() + 4 * nseg);
+  if (!dev_tab.defined() || dev_tab.device() != dev || key != host_key) {
+    at::Tensor ht = at::empty({(int64_t)key.size()}, at::TensorOptions().dtype(at::kInt));
+    std::memcpy(ht.data_ptr<int32_t>(), key.data(), sizeof(int32_t) * key.size());
+    dev_tab = ht.to(dev);
+    host_key = std::move(key);
+  }
+  return dev_tab;
+}
+
 // Causal attention of query segments over the paged bf16 cache (csrc/kernels/prefill_paged.hip):
 // q [T, Hq, 128], pools [blocks, Hkv, blk, 128], block_table int32 [slots, maxb], segs int32 [nseg, 4]
 // = (first q row, n, slot, p0) -> out [T, Hq * 128]; rows outside every segment are not written.
@@ -1029,26 +1048,74 @@ at::Tensor prefill_attn_paged(const at::Tensor& q, const at::Tensor& k_cache, co
            T, ", Hq ", Hq, ", Hkv ", L.Hkv, ", D ", D, ", blk ", L.blk, ", slots ", L.slots, ", maxb ", L.maxb, ", ", nseg,
            " segments");
 
-  static std::mutex mu;
-  static std::vector<int32_t> host_key;
-  static at::Tensor dev_tab;
-  at::Tensor tab;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    std::vector<int32_t> key((size_t)(4 * nseg + 2 * L.nwork));
-    std::memcpy(key.data(), sp, sizeof(int32_t) * 4 * (size_t)nseg);
-    mx::pp_fill_work(sp, nseg, key.data() + 4 * nseg);
-    if (!dev_tab.defined() || dev_tab.device() != q.device() || key != host_key) {
-      at::Tensor ht = at::empty({(int64_t)key.size()}, at::TensorOptions().dtype(at::kInt));
-      std::memcpy(ht.data_ptr<int32_t>(), key.data(), sizeof(int32_t) * key.size());
-      dev_tab = ht.to(q.device());
-      host_key = std::move(key);
-    }
-    tab = dev_tab;
-  }
+  const at::Tensor tab = pp_device_tables(sp, nseg, L.nwork, q.device());
   L.segs = tab.data_ptr<int32_t>();
   L.work = L.segs + 4 * nseg;
   MX_OK(mx_prefill_attn_paged(L, (float)scale, cur_stream()));
+  return o;
+}
+
+// prefill_attn_paged over the fp8 KV cache (csrc/kernels/prefill_paged_kv8.hip): code pools uint8
+// [blocks, Hkv, blk, 128] with float32 scale pools [blocks, Hkv, blk].  Same segments, work table and
+// output as prefill_attn_paged; mx::pp8_takes (kernels/prefill_paged_kv8_args.h) decides on the host
+// before anything is uploaded or enqueued, so a refused call writes nothing.
+at::Tensor prefill_attn_paged_kv8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& k_scale,
+                                  const at::Tensor& v_codes, const at::Tensor& v_scale, const at::Tensor& block_table,
+                                  const at::Tensor& segs, double scale, const c10::optional<at::Tensor>& out) {
+  const char* op = "prefill_attn_paged_kv8";
+  MX_CHECK(q.is_cuda() && q.dim() == 3 && q.is_contiguous(), op, ": q must be a contiguous GPU tensor [T, Hq, D]");
+  for (const at::Tensor* t : {&k_codes, &k_scale, &v_codes, &v_scale})
+    MX_CHECK(t->defined() && t->device() == q.device() && t->dim() >= 1 && t->dim() <= 4, op,
+             ": the four pools must be tensors of 1 to 4 dimensions on q's device");
+  MX_CHECK(block_table.device() == q.device() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+               block_table.is_contiguous(),
+           op, ": block_table must be a contiguous int32 [slots, max_blocks] tensor on q's device");
+  MX_CHECK(segs.scalar_type() == at::kInt && segs.dim() == 2 && segs.size(1) == 4, op,
+           ": segs must be int32 [nseg, 4] = (first q row, n, slot, p0)");
+  const int64_t T = q.size(0), Hq = q.size(1), D = q.size(2);
+  if (out.has_value() && out->defined())
+    MX_CHECK(out->device() == q.device() && out->dim() == 2 && out->size(0) == T && out->size(1) == Hq * D &&
+                 out->stride(1) == 1,
+             op, ": out must be [T, Hq * D] rows on q's device");
+  const at::Tensor sh = segs.cpu().contiguous();
+  const int64_t nseg = sh.size(0);
+  DevGuard g(q.device());
+  at::Tensor o = out.has_value() && out->defined() ? *out : at::empty({T, Hq * D}, q.options());
+  if (nseg == 0 || T == 0) return o;
+  const auto* sp = reinterpret_cast<const mx::PpSeg*>(sh.data_ptr<int32_t>());
+
+  auto pool = [](const at::Tensor& t, at::ScalarType want) {
+    mx::Pp8Pool p{};
+    p.p = t.data_ptr();
+    p.dtype_ok = t.scalar_type() == want;
+    p.contiguous = t.is_contiguous();
+    p.ndim = (int)t.dim();
+    for (int64_t d = 0; d < t.dim(); ++d) p.dim[d] = t.size(d);
+    return p;
+  };
+  mx::PpKv8Launch L{};
+  L.q = q.data_ptr();
+  L.k_codes = pool(k_codes, at::kByte), L.k_scale = pool(k_scale, at::kFloat);
+  L.v_codes = pool(v_codes, at::kByte), L.v_scale = pool(v_scale, at::kFloat);
+  L.o = o.data_ptr();
+  L.bt = block_table.data_ptr<int32_t>();
+  L.segs_host = sp;
+  L.q_bf16 = q.scalar_type() == at::kBFloat16;
+  L.o_bf16 = o.scalar_type() == at::kBFloat16;
+  L.T = T, L.Hq = Hq, L.D = D;
+  L.slots = block_table.size(0), L.maxb = block_table.size(1);
+  L.nseg = nseg, L.nwork = mx::pp_work_count(sp, nseg), L.ldo = o.stride(0);
+  // the check runs on placeholders of the two device tables first: nothing is uploaded for a refused call
+  L.segs = L.work = L.bt;
+  MX_CHECK(mx::pp8_takes(L), op,
+           ": the kernel does not take this call (mx::pp8_takes, csrc/kernels/prefill_paged_kv8_args.h): T ", T, ", Hq ",
+           Hq, ", D ", D, ", code pools ", k_codes.sizes(), " ", k_codes.scalar_type(), " / ", v_codes.sizes(), " ",
+           v_codes.scalar_type(), ", scale pools ", k_scale.sizes(), " ", k_scale.scalar_type(), " / ", v_scale.sizes(),
+           " ", v_scale.scalar_type(), ", slots ", L.slots, ", maxb ", L.maxb, ", ", nseg, " segments");
+  const at::Tensor tab = pp_device_tables(sp, nseg, L.nwork, q.device());
+  L.segs = tab.data_ptr<int32_t>();
+  L.work = L.segs + 4 * nseg;
+  MX_OK(mx_prefill_attn_paged_kv8(L, (float)scale, cur_stream()));
   return o;
 }
 
@@ -1834,6 +1901,7 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None, Tensor? counters=None) -> Tensor");
   m.def("decode_attn_partials(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> (Tensor, Tensor)");
   m.def("prefill_attn_paged(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_table, Tensor segs, float scale, Tensor? out=None) -> Tensor");
+  m.def("prefill_attn_paged_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor block_table, Tensor segs, float scale, Tensor? out=None) -> Tensor");
   m.def("kv8_quant_rows(Tensor x) -> (Tensor, Tensor)");
   m.def("rope_append_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor? slots, Tensor(a!) k_codes, Tensor(b!) k_scale, Tensor(c!) v_codes, Tensor(d!) v_scale, int Hq, int Hkv, Tensor? block_table=None) -> Tensor");
   m.def("decode_attn_kv8(Tensor q, Tensor k_codes, Tensor k_scale, Tensor v_codes, Tensor v_scale, Tensor lens, Tensor? slots, int max_len, float scale, int len_off=0, Tensor? block_table=None) -> Tensor");
@@ -1905,6 +1973,7 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("skinny_merge_linear", &skinny_merge_linear);
   m.impl("decode_attn", &decode_attn);
   m.impl("prefill_attn_paged", &prefill_attn_paged);
+  m.impl("prefill_attn_paged_kv8", &prefill_attn_paged_kv8);
   m.impl("kv8_quant_rows", &kv8_quant_rows);
   m.impl("rope_append_kv8", &rope_append_kv8);
   m.impl("decode_attn_kv8", &decode_attn_kv8);

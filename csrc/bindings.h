@@ -11,6 +11,7 @@
 #include "kernels/attn_args.h"
 #include "kernels/gemm8_args.h"
 #include "kernels/prefill_paged_args.h"
+#include "kernels/prefill_paged_kv8_args.h"
 #include "kernels/skinny_args.h"
 #include "kernels/verify_args.h"
 #include "kernels/w4_args.h"
@@ -150,6 +151,9 @@ int mx_peer_collective(int mode, int dtype, char* const* bases, const void* in, 
 
 // prefill_paged.hip (operand rules: mx::pp_takes, kernels/prefill_paged_args.h)
 int mx_prefill_attn_paged(const mx::PpLaunch& L, float scale, hipStream_t stream);
+
+// prefill_paged_kv8.hip (operand rules: mx::pp8_takes, kernels/prefill_paged_kv8_args.h)
+int mx_prefill_attn_paged_kv8(const mx::PpKv8Launch& L, float scale, hipStream_t stream);
 
 // rmsnorm.hip
 int mx_rmsnorm_fwd(const uint16_t* x, const uint16_t* res, const uint16_t* w, uint16_t* y,

@@ -34,9 +34,12 @@ ARCH = os.environ.get("MXLLM_ARCH", "gfx950")
 
 # per-kernel-file compiler options (A/B experiments: MXLLM_FILE_FLAGS="file.hip=-opt1 -opt2;other.hip=...")
 # mxfp4_gemm.hip: no packed-f32 VALU forms (v_pk_add_f32 and kin) -- its f32x4 sums (the LDS reduction, the
-# K-split sum pass) are compiled to plain per-component adds
+# K-split sum pass) are compiled to plain per-component adds; prefill_paged_kv8.hip: the same for its f32x16
+# accumulator rescale and the scale products of the kv8 decode
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 PER_FILE_HIP_FLAGS: dict[str, list[str]] = {
-    "mxfp4_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "mxfp4_gemm.hip": list(_NO_PK_F32),
+    "prefill_paged_kv8.hip": list(_NO_PK_F32),
 }
 for _item in filter(None, os.environ.get("MXLLM_FILE_FLAGS", "").split(";")):
     _f, _, _opts = _item.partition("=")

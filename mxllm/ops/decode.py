@@ -4,7 +4,8 @@ GPU: csrc/kernels/decode.hip (rope_append, split-K decode attention, their kv8
 forms over an fp8 KV cache, the multi-row verify attention of speculative decoding,
 greedy / Gumbel-max sampler), sampling.hip (batched top-k / top-p / temperature, draft acceptance),
 logits_proc.hip (sampling penalties, logit_bias, log-probabilities),
-attn_fwd.hip for prefill and prefill_paged.hip for prefill chunks over the paged cache.
+attn_fwd.hip for prefill and prefill_paged.hip / prefill_paged_kv8.hip for prefill chunks over the
+paged bf16 / fp8 cache.
 CPU: reference implementations.
 """
 from __future__ import annotations
@@ -85,11 +86,14 @@ class PrefillPlan:
         self.bt_host = block_table.cpu() if block_table is not None else None
 
 
-def prefill_paged_route(D: int, Hq: int, Hkv: int, blk: int, dtype) -> str:
-    """GPU route of ``prefill_attention_paged``: "hip" (csrc/kernels/prefill_paged.hip) where the
-    kernel takes the launch -- bf16, head_dim 128, whole GQA groups of at most 16, a block size
-    that is a multiple of 256 -- else "gather".  ``MXLLM_PREFILL_PAGED=hip|gather`` forces one;
-    a forced "hip" that the kernel does not take is an error, not a fall-back."""
+def prefill_paged_route(D: int, Hq: int, Hkv: int, blk: int, dtype, kv8: bool = False) -> str:
+    """GPU route of ``prefill_attention_paged``: "hip" (csrc/kernels/prefill_paged.hip, over a kv8
+    cache prefill_paged_kv8.hip) where the kernel takes the launch -- bf16 queries, head_dim 128,
+    whole GQA groups of at most 16, a block size that is a multiple of 256 -- else "gather".  The
+    rules are the same for both cache formats (``kv8``: the pools are fp8 code pools), and so is
+    the default: the kv8 kernel measured faster than gather-and-dequantise at every context length
+    (profiles/prefix_cache/README.md).  ``MXLLM_PREFILL_PAGED=hip|gather`` forces one; a forced
+    "hip" that the kernel does not take is an error, not a fall-back."""
     env = os.environ.get("MXLLM_PREFILL_PAGED", "")
     if env:
         if env not in ("hip", "gather"):
@@ -100,16 +104,22 @@ def prefill_paged_route(D: int, Hq: int, Hkv: int, blk: int, dtype) -> str:
 
 
 def paged_attention_gather(q: torch.Tensor, k_cache, v_cache, bt_host, segs, scale: float,
-                           out: torch.Tensor) -> torch.Tensor:
+                           out: torch.Tensor, k_scale: torch.Tensor | None = None,
+                           v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """The gather route of ``prefill_attention_paged`` (GPU, any head dim ``attn_fwd`` takes): per
     segment ``(row0, n, slot, p0)`` the rows [0, p0 + n) of the slot are made contiguous (``_kv_at``
     through the HOST block table) and fed to ``attn_fwd`` with Sk = p0 + n > S = n, whose causal
-    offset Sk - S is p0.  q [T, Hq, D] (rope_append's output) -> rows of ``out`` [T, Hq * D]."""
+    offset Sk - S is p0.  q [T, Hq, D] (rope_append's output) -> rows of ``out`` [T, Hq * D].
+    ``k_scale`` / ``v_scale``: kv8 pools, whose gathered rows are dequantised to bf16 first."""
     ops = native()
     Hq, D = q.shape[1], q.shape[2]
+    deq = _kv8_codec()[1] if k_scale is not None else None
     for row0, n, slot, p0 in segs:
-        kk = _kv_at(k_cache, bt_host, slot, 0, p0 + n).contiguous().unsqueeze(0)
-        vv = _kv_at(v_cache, bt_host, slot, 0, p0 + n).contiguous().unsqueeze(0)
+        kk, vv = _kv_at(k_cache, bt_host, slot, 0, p0 + n), _kv_at(v_cache, bt_host, slot, 0, p0 + n)
+        if deq is not None:
+            kk = deq(kk, _kv_at(k_scale, bt_host, slot, 0, p0 + n))
+            vv = deq(vv, _kv_at(v_scale, bt_host, slot, 0, p0 + n))
+        kk, vv = kk.contiguous().unsqueeze(0), vv.contiguous().unsqueeze(0)
         qs = q[row0:row0 + n].transpose(0, 1).contiguous().unsqueeze(0)  # [1, Hq, n, D]
         o, _ = ops.attn_fwd(qs, kk, vv, True, scale)
         out[row0:row0 + n] = o.view(n, Hq * D)
@@ -117,7 +127,8 @@ def paged_attention_gather(q: torch.Tensor, k_cache, v_cache, bt_host, segs, sca
 
 
 def prefill_attention_paged(qkv: torch.Tensor, cos, sin, k_cache, v_cache, block_table, segs, Hq: int, Hkv: int,
-                            D: int, out: torch.Tensor | None = None) -> torch.Tensor:
+                            D: int, out: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                            v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """Prefill chunks over the paged KV cache.  qkv [T, NH*D]; ``segs`` a host list of
     ``(row0, n, slot, p0)`` (or a ``PrefillPlan`` of it, built once per pass): rows
     [row0, row0 + n) are positions [p0, p0 + n) of cache slot ``slot``.  RoPE and the cache append
@@ -127,7 +138,18 @@ def prefill_attention_paged(qkv: torch.Tensor, cos, sin, k_cache, v_cache, block
 
     GPU routes (``prefill_paged_route``): "hip" -- one launch of the paged flash-attention kernel
     for all segments; "gather" -- per segment, rows [0, p0 + n) made contiguous (``_kv_at``) and
-    ``attn_fwd`` with Sk > S (its causal offset Sk - S is p0).  CPU: the fp32 softmax expression."""
+    ``attn_fwd`` with Sk > S (its causal offset Sk - S is p0).  CPU: the fp32 softmax expression.
+
+    ``k_scale`` / ``v_scale``: the caches are kv8 code pools with these scale pools (fp8 KV cache,
+    head_dim 128).  The append is ``rope_append_kv8``, "hip" is the kv8 kernel
+    (prefill_paged_kv8.hip: codes decoded on their way into LDS), "gather" dequantises the gathered
+    rows to bf16, and the CPU expression runs over the dequantised rows."""
+    kv8 = k_scale is not None or v_scale is not None
+    if kv8:
+        if k_scale is None or v_scale is None:
+            raise ValueError("prefill_attention_paged: a kv8 cache needs both k_scale and v_scale")
+        if D != 128:
+            raise ValueError(f"prefill_attention_paged: the fp8 KV cache supports head_dim 128 only, got {D}")
     T = qkv.shape[0]
     plan = segs if isinstance(segs, PrefillPlan) else PrefillPlan(segs, T, qkv.device)
     if plan.T != T:
@@ -139,21 +161,31 @@ def prefill_attention_paged(qkv: torch.Tensor, cos, sin, k_cache, v_cache, block
         return out
     if use_native(qkv):
         ops = native()
-        route = prefill_paged_route(D, Hq, Hkv, k_cache.shape[2], qkv.dtype)
+        route = prefill_paged_route(D, Hq, Hkv, k_cache.shape[2], qkv.dtype, kv8)
         qkv = qkv.contiguous()
+
+        def append(x, pos, slots):
+            if kv8:
+                return ops.rope_append_kv8(x, cos, sin, pos, slots, k_cache, k_scale, v_cache, v_scale, Hq, Hkv,
+                                           block_table)
+            return ops.rope_append(x, cos, sin, pos, slots, k_cache, v_cache, Hq, Hkv, D, block_table)
+
         if plan.dense:
-            q = ops.rope_append(qkv, cos, sin, plan.pos, plan.slots, k_cache, v_cache, Hq, Hkv, D, block_table)
+            q = append(qkv, plan.pos, plan.slots)
         else:  # rows in no segment are neither rotated nor appended
             q = torch.empty(T, Hq, D, dtype=qkv.dtype, device=qkv.device)
             for row0, n, _, _ in plan.segs:
-                q[row0:row0 + n] = ops.rope_append(qkv[row0:row0 + n], cos, sin, plan.pos[row0:row0 + n].contiguous(),
-                                                   plan.slots[row0:row0 + n].contiguous(), k_cache, v_cache, Hq, Hkv,
-                                                   D, block_table)
+                q[row0:row0 + n] = append(qkv[row0:row0 + n], plan.pos[row0:row0 + n].contiguous(),
+                                          plan.slots[row0:row0 + n].contiguous())
         if route == "hip":
+            if kv8:
+                return ops.prefill_attn_paged_kv8(q, k_cache, k_scale, v_cache, v_scale, block_table, plan.table,
+                                                  scale, out)
             return ops.prefill_attn_paged(q, k_cache, v_cache, block_table, plan.table, scale, out)
         if plan.bt_host is None:
             plan.bt_host = block_table.cpu()
-        return paged_attention_gather(q, k_cache, v_cache, plan.bt_host, plan.segs, scale, out)
+        return paged_attention_gather(q, k_cache, v_cache, plan.bt_host, plan.segs, scale, out, k_scale, v_scale)
+    quant, deq = _kv8_codec() if kv8 else (None, None)
     bt = block_table.cpu() if block_table is not None else None
     x = qkv.view(T, Hq + 2 * Hkv, D).float()
     for row0, n, slot, p0 in plan.segs:
@@ -166,17 +198,24 @@ def prefill_attention_paged(qkv: torch.Tensor, cos, sin, k_cache, v_cache, block
 
         xs = x[row0:row0 + n]
         qi = rot(xs[:, :Hq]).to(qkv.dtype).float()  # [n, Hq, D], rounded as rope_append stores it
-        ki = rot(xs[:, Hq:Hq + Hkv]).to(k_cache.dtype)
-        vi = qkv.view(T, Hq + 2 * Hkv, D)[row0:row0 + n, Hq + Hkv:].to(v_cache.dtype)
+        ki = rot(xs[:, Hq:Hq + Hkv]).to(qkv.dtype if kv8 else k_cache.dtype)
+        vi = qkv.view(T, Hq + 2 * Hkv, D)[row0:row0 + n, Hq + Hkv:].to(qkv.dtype if kv8 else v_cache.dtype)
         blk = k_cache.shape[2] if bt is not None else None
         a = 0
         while a < n:  # the chunk's own rows, block by block
             e = n if blk is None else min(n, ((p0 + a) // blk + 1) * blk - p0)
-            _kv_at(k_cache, bt, slot, p0 + a, p0 + e).copy_(ki[a:e].transpose(0, 1))
-            _kv_at(v_cache, bt, slot, p0 + a, p0 + e).copy_(vi[a:e].transpose(0, 1))
+            for cache, sc_pool, rows in ((k_cache, k_scale, ki), (v_cache, v_scale, vi)):
+                rows = rows[a:e].transpose(0, 1)
+                if kv8:  # the chunk's rows through kv8_quantize, as rope_append_kv8 stores them
+                    rows, sc_rows = quant(rows.contiguous())
+                    _kv_at(sc_pool, bt, slot, p0 + a, p0 + e).copy_(sc_rows)
+                _kv_at(cache, bt, slot, p0 + a, p0 + e).copy_(rows)
             a = e
-        kk = _kv_at(k_cache, bt, slot, 0, p0 + n).float().repeat_interleave(Hq // Hkv, 0)  # [Hq, L, D]
-        vv = _kv_at(v_cache, bt, slot, 0, p0 + n).float().repeat_interleave(Hq // Hkv, 0)
+        kk, vv = _kv_at(k_cache, bt, slot, 0, p0 + n), _kv_at(v_cache, bt, slot, 0, p0 + n)
+        if kv8:
+            kk, vv = deq(kk, _kv_at(k_scale, bt, slot, 0, p0 + n)), deq(vv, _kv_at(v_scale, bt, slot, 0, p0 + n))
+        kk = kk.float().repeat_interleave(Hq // Hkv, 0)  # [Hq, L, D]
+        vv = vv.float().repeat_interleave(Hq // Hkv, 0)
         sc = torch.einsum("nhd,hld->hnl", qi, kk) * scale
         key = torch.arange(p0 + n).view(1, 1, -1)
         row = torch.arange(n).view(1, -1, 1)

@@ -194,7 +194,9 @@ class Engine:
         long prompt no longer stalls streaming requests for its whole prefill.  With either option
         every prefill runs through ``prefill_segments`` (``dops.prefill_attention_paged``: attention
         of a chunk over the rows already in the block pool); with both off nothing changes.
-        Neither works with ``kv_dtype="fp8"`` or ``tp_group`` yet (ValueError).  Two new requests of
+        Both work over either ``kv_dtype`` (fp8: ``rope_append_kv8`` and the kv8 paged prefill kernel, which
+        decodes the codes on their way into LDS; GPU engines only: an fp8 engine on a CPU device refuses them,
+        ValueError); neither works with ``tp_group`` yet (ValueError).  Two new requests of
         ONE admission pass that share a prefix both miss: blocks are registered when a prompt completes.
         ``speculate`` = K (None: env MXLLM_SPECULATE; 0 / None: off): speculative decoding with up to K
         drafted tokens per request and step (``verify``; the module docstring).  ``drafter``: any
@@ -281,8 +283,9 @@ class Engine:
         if kv_dtype == "fp8" and c.head_dim != 128:
             raise ValueError(f"the fp8 KV cache supports head_dim 128 only; this model has head_dim {c.head_dim}")
         self.kv_dtype = kv_dtype
-        if self.paged_prefill and kv_dtype == "fp8":
-            raise ValueError("prefix_cache / prefill_chunk are not supported over the fp8 KV cache yet")
+        if self.paged_prefill and kv_dtype == "fp8" and self.device.type != "cuda":
+            raise ValueError("prefix_cache / prefill_chunk over the fp8 KV cache run on the GPU only "
+                             "(csrc/kernels/prefill_paged_kv8.hip); on a CPU device use the bf16 KV cache")
         if self.prefix_cache and kv_pool_tokens is None:
             raise ValueError("prefix_cache needs the paged KV cache (kv_pool_tokens / MXLLM_KV_POOL_TOKENS)")
         self.kv = KVCache(c.n_layers, c.n_kv_heads, c.head_dim, dt, self.device, n_slots, self.max_seq,
@@ -538,8 +541,8 @@ class Engine:
         of the chunk, then causal attention of each chunk over its slot's rows in the block pool.
         Returns the last-row logits of each chunk [n, V] f32.  ``adapters`` as in ``prefill_batch``."""
         m, c = self.model, self.cfg
-        if self.kv.fp8 or self.tp is not None:
-            raise NotImplementedError("prefill_segments: bf16 KV cache, single GPU")
+        if self.tp is not None:
+            raise NotImplementedError("prefill_segments: single GPU")
         ns = [len(ch) for ch in chunks]
         if not (len(slots) == len(chunks) == len(starts)) or any(n <= 0 for n in ns) or any(st < 0 for st in starts):
             raise ValueError("prefill_segments: one non-empty chunk and one start >= 0 per slot")
@@ -560,9 +563,13 @@ class Engine:
         plan = dops.PrefillPlan([(offs[j], ns[j], slots[j], starts[j]) for j in range(len(chunks))], offs[-1],
                                 self.device, block_table=self.kv.bt_host)
 
+        fp8 = self.kv.fp8
+
         def attn(i, qkv):
             return dops.prefill_attention_paged(qkv, m.rope_cos, m.rope_sin, self.kv.k[i], self.kv.v[i], self.kv.bt,
-                                                plan, c.n_heads, c.n_kv_heads, c.head_dim)
+                                                plan, c.n_heads, c.n_kv_heads, c.head_dim,
+                                                k_scale=self.kv.k_scale[i] if fp8 else None,
+                                                v_scale=self.kv.v_scale[i] if fp8 else None)
 
         lora = None
         if any(a >= 0 for a in aidx):

@@ -401,10 +401,10 @@ def parse_args(argv=None):
                     help="paged KV cache: a pool of that many tokens shared by all slots (env MXLLM_KV_POOL_TOKENS)")
     ap.add_argument("--prefix-cache", action="store_true", default=None,
                     help="share the KV blocks of common prompt prefixes between requests (needs the paged KV "
-                         "cache: --kv-pool-tokens; bf16 KV cache, --tp 1; env MXLLM_PREFIX_CACHE=1)")
+                         "cache: --kv-pool-tokens; either --kv-cache; --tp 1; env MXLLM_PREFIX_CACHE=1)")
     ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
                     help="prefill at most N prompt tokens per engine step, so a long prompt does not stall the "
-                         "streaming requests (bf16 KV cache, --tp 1; env MXLLM_PREFILL_CHUNK)")
+                         "streaming requests (either --kv-cache; --tp 1; env MXLLM_PREFILL_CHUNK)")
     ap.add_argument("--speculative-ngram", type=int, default=None, metavar="K",
                     help="speculative decoding: verify up to K tokens per request and step, drafted by n-gram "
                          "lookup in the request's own prompt and output (no draft model; --tp 1; K + 1 times the "
