@@ -25,7 +25,39 @@ def timeit(fn, iters=20):
     return a.elapsed_time(b) / iters
 
 
+def doc_rounds(ops, q, k, v, sc, n_docs, rounds=7):
+    """``--docs N``: the document-masked kernels (N equal documents per sequence) against the plain
+    causal ones (split backward, f32 dQ), alternating round by round in one process; medians."""
+    B, Hq, S, D = q.shape
+    pos = torch.arange(S, device=q.device, dtype=torch.int32)
+    L = (S + n_docs - 1) // n_docs
+    ds = (pos // L * L).expand(B, S).contiguous()
+    de = torch.clamp(ds + L, max=S).contiguous()
+    o, lse = ops.attn_fwd(q, k, v, True, sc)
+    od, lsed = ops.attn_doc_fwd(q, k, v, ds, sc)
+    do = torch.randn_like(o)
+    runs = {"fwd_ms": lambda: ops.attn_fwd(q, k, v, True, sc),
+            "doc_fwd_ms": lambda: ops.attn_doc_fwd(q, k, v, ds, sc),
+            "bwd_ms": lambda: ops.attn_bwd(do, q, k, v, o, lse, True, sc, 3),
+            "doc_bwd_ms": lambda: ops.attn_doc_bwd(do, q, k, v, od, lsed, ds, de, sc)}
+    ts = {n: [] for n in runs}
+    for _ in range(rounds):
+        for n, fn in runs.items():
+            ts[n].append(timeit(fn, 10))
+    res = {"shape": [B, Hq, k.shape[1], S, D], "docs": n_docs, "rounds": rounds}
+    res.update({n: sorted(t)[len(t) // 2] for n, t in ts.items()})
+    res.update({n.replace("_ms", "_spread"): (max(t) - min(t)) / sorted(t)[len(t) // 2] for n, t in ts.items()})
+    res["fwd_ratio"], res["bwd_ratio"] = res["doc_fwd_ms"] / res["fwd_ms"], res["doc_bwd_ms"] / res["bwd_ms"]
+    res["ideal_ratio"] = sum(n * (n + 1) / 2 for n in [min(L, S - s) for s in range(0, S, L)]) / (S * (S + 1) / 2)
+    print(json.dumps({k2: (round(v2, 4) if isinstance(v2, float) else v2) for k2, v2 in res.items()}), flush=True)
+
+
 def main():
+    n_docs = 0
+    if "--docs" in sys.argv:
+        i = sys.argv.index("--docs")
+        n_docs = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
     B, Hq, Hkv, S, D = [int(x) for x in (sys.argv[1:6] if len(sys.argv) > 5 else (2, 64, 8, 2048, 128))]
     ops = native()
     dev = "cuda"
@@ -33,6 +65,8 @@ def main():
     k = torch.randn(B, Hkv, S, D, device=dev, dtype=torch.bfloat16)
     v = torch.randn(B, Hkv, S, D, device=dev, dtype=torch.bfloat16)
     sc = 1 / math.sqrt(D)
+    if n_docs:
+        return doc_rounds(ops, q, k, v, sc, n_docs)
     o, lse = ops.attn_fwd(q, k, v, True, sc)
     do = torch.randn_like(o)
     fl = 2 * 2 * B * Hq * S * S * D / 2

@@ -846,6 +846,72 @@ at::Tensor attn_bwd_rope(const at::Tensor& dout, const at::Tensor& q, const at::
   return dqkv;
 }
 
+// ---------------------------------------------------------------- document-masked attention
+// Packed sequences: query i sees key j iff doc_start[b, i] <= j <= i (tables [B, S] int32 on q's device,
+// mxllm.ops.doc_bounds).  The rules are mx::ad_takes (kernels/attn_doc_args.h); every operand check runs
+// before anything is allocated or written.
+static mx::AdLaunch attn_doc_fill(const char* op, const mx::AbLaunch& S, const at::Tensor& q,
+                                  const at::Tensor& doc_start, const at::Tensor* doc_end) {
+  MX_CHECK(S.Sk == S.S, op, ": self-attention only (k/v rows ", S.Sk, ", q rows ", S.S, ")");
+  for (auto [n, t] : {std::pair{"doc_start", &doc_start}, {"doc_end", doc_end}}) {
+    if (!t) continue;
+    attn_operand(op, n, *t, q.device(), at::kInt);
+    MX_CHECK(t->dim() == 2 && t->size(0) == S.B && t->size(1) == S.S, op, ": ", n, " must be [B, S], got ", t->sizes());
+  }
+  mx::AdLaunch L{};
+  L.bwd = doc_end ? 1 : 0;
+  L.q = S.q, L.k = S.k, L.v = S.v, L.doc_start = doc_start.data_ptr(), L.doc_end = doc_end ? doc_end->data_ptr() : nullptr;
+  L.q_bf16 = L.kv_bf16 = L.o_bf16 = L.lse_f32 = L.doc_i32 = 1, L.dout_bf16 = L.out_f32 = L.bwd;
+  L.B = S.B, L.Hq = S.Hq, L.Hkv = S.Hkv, L.S = S.S, L.D = S.D, L.ldo = S.ldo;
+  return L;
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_doc_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                const at::Tensor& doc_start, double scale, int64_t out_pad) {
+  mx::AbLaunch S = attn_fill("attn_doc_fwd", q, k, v, true);
+  MX_CHECK(out_pad >= 0 && out_pad % 8 == 0, "out_pad must be a non-negative multiple of 8");
+  S.ldo += out_pad;
+  mx::AdLaunch L = attn_doc_fill("attn_doc_fwd", S, q, doc_start, nullptr);
+  DevGuard g(q.device());
+  auto o = at::empty({S.B, S.S, S.ldo}, q.options()).narrow(2, 0, S.Hq * S.D);
+  auto lse = at::empty({S.B, S.Hq, S.S}, q.options().dtype(at::kFloat));
+  L.o = o.data_ptr(), L.lse = lse.data_ptr();
+  attn_launched("attn_doc_fwd", mx_attn_doc(L, (float)scale, cur_stream()), S);
+  return {o, lse};
+}
+
+// dq_out / dk_out / dv_out (optional): preallocated f32 dq [B, Hq, S, D] and dK / dV partials [B, Hq, S, D] to
+// write into (head-range views: the chunked backward, mxllm/ops/attention.py)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_doc_bwd(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+    const at::Tensor& lse, const at::Tensor& doc_start, const at::Tensor& doc_end, double scale,
+    const OptTensor& dq_out, const OptTensor& dk_out, const OptTensor& dv_out) {
+  const char* op = "attn_doc_bwd";
+  mx::AbLaunch S = attn_fill(op, q, k, v, true, 3, &o, &dout, &lse);
+  S.hpw = 1;  // one dK / dV partial per q head
+  mx::AdLaunch L = attn_doc_fill(op, S, q, doc_start, &doc_end);
+  const bool outs = dq_out.has_value() || dk_out.has_value() || dv_out.has_value();
+  if (outs) {
+    MX_CHECK(dq_out.has_value() && dk_out.has_value() && dv_out.has_value(), op, ": preallocated outputs need all three");
+    for (auto [n, t] : {std::pair{"dq_out", &*dq_out}, {"dk_out", &*dk_out}, {"dv_out", &*dv_out}}) {
+      attn_operand(op, n, *t, q.device(), at::kFloat);
+      MX_CHECK(t->numel() == q.numel(), op, ": ", n, " must hold [B, Hq, S, D]");
+    }
+  }
+  DevGuard g(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  auto dq = outs ? *dq_out : at::empty({L.B, L.Hq, L.S, L.D}, f32);
+  auto dkp = outs ? *dk_out : at::empty({L.B, L.Hq, L.S, L.D}, f32);
+  auto dvp = outs ? *dv_out : at::empty({L.B, L.Hq, L.S, L.D}, f32);
+  auto delta = at::empty({L.B, L.Hq, L.S}, f32);
+  auto work = at::empty({mx::ad_work_bytes(L)}, q.options().dtype(at::kByte));
+  L.o = const_cast<void*>(S.o), L.lse = const_cast<void*>(S.lse), L.dout = S.dout;
+  L.delta = delta.data_ptr(), L.dq = dq.data_ptr(), L.dkp = dkp.data_ptr(), L.dvp = dvp.data_ptr();
+  L.work = work.data_ptr();
+  attn_launched(op, mx_attn_doc(L, (float)scale, cur_stream()), S);
+  return {dq, dkp, dvp};
+}
+
 // ---------------------------------------------------------------- decode
 // Paged KV caches: k_cache/v_cache [blocks, Hkv, block, D] + block_table int32 [slots, maxb]
 // (token p of slot s in block block_table[s][p / block]); without a block table the caches
@@ -1932,6 +1998,8 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("lora_gather_shrink(Tensor x, Tensor ids, Tensor a_tab, Tensor(a!) partials) -> ()");
   m.def("lora_gather_expand_add_(Tensor(a!) y, Tensor partials, Tensor ids, Tensor b_tab, Tensor s_tab, int[] splits, int K) -> ()");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, int dq_mode=3, Tensor? dq_out=None, Tensor? dk_out=None, Tensor? dv_out=None) -> (Tensor, Tensor, Tensor)");
+  m.def("attn_doc_fwd(Tensor q, Tensor k, Tensor v, Tensor doc_start, float scale, int out_pad=0) -> (Tensor, Tensor)");
+  m.def("attn_doc_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor doc_start, Tensor doc_end, float scale, Tensor? dq_out=None, Tensor? dk_out=None, Tensor? dv_out=None) -> (Tensor, Tensor, Tensor)");
   m.def("attn_bwd_rope(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor cos, Tensor sin, int out_pad=0) -> Tensor");
 }
 
@@ -1968,6 +2036,8 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_bwd_rope", &attn_bwd_rope);
+  m.impl("attn_doc_fwd", &attn_doc_fwd);
+  m.impl("attn_doc_bwd", &attn_doc_bwd);
   m.impl("rope_append", &rope_append);
   m.impl("decode_attn_partials", &decode_attn_partials);
   m.impl("skinny_merge_linear", &skinny_merge_linear);

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "kernels/attn_args.h"
+#include "kernels/attn_doc_args.h"
 #include "kernels/gemm8_args.h"
 #include "kernels/prefill_paged_args.h"
 #include "kernels/prefill_paged_kv8_args.h"
@@ -25,6 +26,10 @@ int mx_attn_bwd(const mx::AbLaunch& L, float scale, hipStream_t stream);
 
 // attn_fwd.hip (operand rules: mx::af_takes, kernels/attn_args.h)
 int mx_attn_fwd(const mx::AfLaunch& L, float scale, hipStream_t stream);
+
+// attn_doc.hip: document-masked forward (L.bwd = 0) or split backward (1); operand rules: mx::ad_takes,
+// kernels/attn_doc_args.h
+int mx_attn_doc(const mx::AdLaunch& L, float scale, hipStream_t stream);
 
 // cross_entropy.hip
 int mx_ce_fwd_bwd(uint16_t* logits, const int64_t* labels, float* losses, float* inv_n, float* loss_out, int64_t T,

@@ -67,6 +67,7 @@ class RunConfig:
     warmup_steps: int = 0
     steps: int = 0  # 0 = run epochs over the dataset
     seq_len: int = 512
+    doc_mask: bool = False  # packed windows: attention inside a document only (Llama.set_document_mask)
     micro_batch: int = 4
     grad_accum: int = 1
     bucket_mb: float = 128.0

@@ -209,6 +209,7 @@ class Llama(nn.Module):
         self.activation_checkpointing = activation_checkpointing
         self.mlp_recompute_ckpt = None  # checkpoint spec of a trainer that runs _layer itself (ZeRO-3)
         self.seq_parallel = None  # UlyssesAttention when the sequence is sharded (set_sequence_parallel)
+        self.doc_eos = None  # EOS id of packed documents: attention stays inside them (set_document_mask)
         # optional ``fn(params)`` called before the parameters are first used in a forward (ZeRO-1: wait for
         # their all-gather; mxllm/parallel/zero1.py) — None = parameters are always resident
         self.param_wait = None
@@ -253,7 +254,9 @@ class Llama(nn.Module):
         """Row padding a producer leaves for a LoRA projection's rank columns."""
         return lin.pad if lin.augmented() else 0
 
-    def _layer(self, i: int, x: torch.Tensor, h: torch.Tensor, B: int, S: int):
+    def _layer(self, i: int, x: torch.Tensor, h: torch.Tensor, B: int, S: int, doc=None):
+        """``doc``: the (doc_start, doc_end) tables of THIS call's micro-batch (``document_tables``), an
+        argument so that a checkpointed layer's recompute sees the tables captured with its inputs."""
         cfg = self.cfg
         layer = self.layers[i]
         rec = self._recompute_m(layer, i)
@@ -265,13 +268,14 @@ class Llama(nn.Module):
             # projection + RoPE + head split in ONE GEMM epilogue (mxllm/ops/fused.py)
             o = fused.qkv_attention(x, layer.wqkv.weight, self.rope_cos, self.rope_sin, B, S, cfg.n_heads,
                                     cfg.n_kv_heads, cfg.head_dim, causal=True, out_pad=self._pad(layer.wo),
-                                    norm=(h, layer.attn_norm, cfg.norm_eps) if rec_x else None)
+                                    norm=(h, layer.attn_norm, cfg.norm_eps) if rec_x else None, doc=doc)
             qkv = None
         elif lora_at:
             # LoRA: the augmented projection with RoPE + head split in its tail-balanced GEMM
             # (mxllm/ops/linear.py lora_qkv_attention): no qkv activation, no rope_split pass
             o = ops.lora_qkv_attention(x, layer.wqkv, self.rope_cos, self.rope_sin, B, S, cfg.n_heads,
-                                       cfg.n_kv_heads, cfg.head_dim, lora_at, causal=True, out_pad=self._pad(layer.wo))
+                                       cfg.n_kv_heads, cfg.head_dim, lora_at, causal=True, out_pad=self._pad(layer.wo),
+                                       doc=doc)
             qkv = None
         else:
             qkv = (ops.normed_linear(x, h, layer.attn_norm, cfg.norm_eps, layer.wqkv.weight) if rec_x
@@ -279,12 +283,14 @@ class Llama(nn.Module):
         if qkv is None:
             pass
         elif self.seq_parallel is not None:
+            if doc is not None:
+                raise ValueError("the document mask does not run with sequence / context parallelism")
             o = self.seq_parallel(qkv, self.rope_cos, self.rope_sin, B, S, cfg.n_heads, cfg.n_kv_heads,
                                   cfg.head_dim, causal=True)
         else:
             o = ops.attention_block(qkv, self.rope_cos, self.rope_sin, B, S, cfg.n_heads, cfg.n_kv_heads,
                                     cfg.head_dim, causal=True, out_pad=self._pad(layer.wo),
-                                    grad_pad=self._pad(layer.wqkv))
+                                    grad_pad=self._pad(layer.wqkv), doc=doc)
         a = layer.wo(o)
         x, h = ops.add_rms_norm(a, h, layer.mlp_norm, cfg.norm_eps, out_pad=self._pad(layer.wgu),
                                 grad_pad=self._pad(layer.wo))
@@ -359,6 +365,7 @@ class Llama(nn.Module):
     def hidden_states(self, ids: torch.Tensor) -> torch.Tensor:
         """ids [B, S] -> final normed hidden [B*S, H]."""
         B, S = ids.shape
+        doc = self.document_tables(ids)
         wait = self.param_wait
         groups = self._wait_groups() if wait is not None else None
         if wait is not None:
@@ -370,9 +377,9 @@ class Llama(nn.Module):
             if wait is not None:
                 wait(groups[i + 1])
             if ckpt_layer(self.activation_checkpointing, i) and self.training and torch.is_grad_enabled():
-                x, h = ckpt.checkpoint(self._layer, i, x, h, B, S, use_reentrant=False)
+                x, h = ckpt.checkpoint(self._layer, i, x, h, B, S, doc, use_reentrant=False)
             else:
-                x, h = self._layer(i, x, h, B, S)
+                x, h = self._layer(i, x, h, B, S, doc)
         if not len(self.layers):
             x = ops.rms_norm(h, self.final_norm, self.cfg.norm_eps)
         if wait is not None:
@@ -419,6 +426,23 @@ class Llama(nn.Module):
             if isinstance(m, FusedLinear):
                 m.refresh_images_()
 
+    def set_document_mask(self, eos_id: int | None) -> None:
+        """Packed documents: with ``eos_id`` set, every training forward builds the document tables of
+        its ids (``ops.doc_bounds``: a document ends with its EOS) and attention stays inside a document
+        (csrc/kernels/attn_doc.hip); ``None`` (default) turns it off.  Positions and labels are unchanged.
+        Not with sequence / context parallelism."""
+        if eos_id is not None and self.seq_parallel is not None:
+            raise ValueError("the document mask does not run with sequence / context parallelism")
+        self.doc_eos = None if eos_id is None else int(eos_id)
+
+    def document_tables(self, ids: torch.Tensor):
+        """(doc_start, doc_end) of one micro-batch's ids, or None when the document mask is off."""
+        return None if self.doc_eos is None else ops.doc_bounds(ids, self.doc_eos)
+
+    def _no_document_mask(self) -> None:
+        if self.doc_eos is not None:
+            raise ValueError("sequence / context parallelism does not run with the document mask")
+
     def set_sequence_parallel(self, group) -> None:
         """Shard sequences over ``group`` (Ulysses all-to-all around attention,
         mxllm/parallel/sequence.py); ``None`` turns it off.  Inputs passed to
@@ -426,6 +450,7 @@ class Llama(nn.Module):
         if group is None:
             self.seq_parallel = None
             return
+        self._no_document_mask()
         from ..parallel.sequence import UlyssesAttention
 
         self.seq_parallel = UlyssesAttention(group)
@@ -437,6 +462,7 @@ class Llama(nn.Module):
         if group is None:
             self.seq_parallel = None
             return
+        self._no_document_mask()
         from ..parallel.context import RingAttention
 
         self.seq_parallel = RingAttention(group)

@@ -65,8 +65,8 @@ class _QKVAttentionFn(torch.autograd.Function):
     ``norm`` = (h, nw, eps): x = rmsnorm(h) nw is NOT saved but recomputed for dW."""
 
     @staticmethod
-    def forward(ctx, x, w, cos, sin, B, S, Hq, Hkv, D, causal, out_pad, h, nw, eps):
-        from .attention import _AttnBlockFn  # noqa: F401  (same kernels, same saved layout)
+    def forward(ctx, x, w, cos, sin, B, S, Hq, Hkv, D, causal, out_pad, h, nw, eps, doc=None):
+        from .attention import attn_forward  # (same kernels, same saved layout as _AttnBlockFn)
 
         ops = native()
         x2 = _x2(x)
@@ -76,9 +76,9 @@ class _QKVAttentionFn(torch.autograd.Function):
         v = torch.empty_like(k)
         if not ops.gemm8_rope(x2, w, cos, sin, B, S, Hq, Hkv, q, k, v):
             raise RuntimeError("gemm8_rope declined a shape qkv_attention_ok accepted")
-        o, lse = ops.attn_fwd(q, k, v, causal, 1.0 / math.sqrt(D), out_pad)
+        o, lse = attn_forward(q, k, v, causal, out_pad, doc)
         keep_x = h is None
-        ctx.save_for_backward(x2 if keep_x else h, w, q, k, v, o, lse, cos, sin, nw)
+        ctx.save_for_backward(x2 if keep_x else h, w, q, k, v, o, lse, cos, sin, nw, *(doc or ()))
         ctx.wp = w if w.is_leaf else None
         ctx.dims = (B, S, Hq, Hkv, D, causal, x.shape, keep_x, eps)
         return o.view(B * S, Hq * D)
@@ -87,26 +87,26 @@ class _QKVAttentionFn(torch.autograd.Function):
     def backward(ctx, do):
         from .attention import backward_dqkv
 
-        xs, w, q, k, v, o, lse, cos, sin, nw = ctx.saved_tensors
+        xs, w, q, k, v, o, lse, cos, sin, nw, *doc = ctx.saved_tensors
         B, S, Hq, Hkv, D, causal, xshape, keep_x, eps = ctx.dims
-        dqkv = backward_dqkv(do, q, k, v, o, lse, cos, sin, causal, 0)
+        dqkv = backward_dqkv(do, q, k, v, o, lse, cos, sin, causal, 0, doc=tuple(doc) or None)
         del q, k, v, o, lse
         dx = gemm.mm("nn", dqkv, w).view(xshape) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             x2 = xs if keep_x else _norm_input(xs, nw, eps)
             dw = param_weight_grad(ctx.wp, dqkv, x2)
-        return dx, dw, None, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def qkv_attention(x: torch.Tensor, w: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, S: int,
                   Hq: int, Hkv: int, D: int, causal: bool = True, out_pad: int = 0,
-                  norm: tuple | None = None) -> torch.Tensor:
+                  norm: tuple | None = None, doc=None) -> torch.Tensor:
     """[B*S, H] -> attention output [B*S, Hq*D] through the fused qkv epilogue (callers check
     ``qkv_attention_ok``).  ``norm`` = (h, nw, eps) when x = rmsnorm(h) nw should be recomputed
-    in the backward instead of saved."""
+    in the backward instead of saved.  ``doc``: the packed-document tables (``ops.doc_bounds``)."""
     h, nw, eps = norm if norm is not None else (None, None, 0.0)
-    return _QKVAttentionFn.apply(x, w, cos, sin, B, S, Hq, Hkv, D, causal, out_pad, h, nw, eps)
+    return _QKVAttentionFn.apply(x, w, cos, sin, B, S, Hq, Hkv, D, causal, out_pad, h, nw, eps, doc)
 
 
 def gate_up_swiglu_ok(x: torch.Tensor, w: torch.Tensor) -> bool:

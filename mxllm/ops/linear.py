@@ -285,7 +285,9 @@ class _LoRAQKVAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, b, wbuf, scaling, splits, r, pad, wbt, wxt, cos, sin, B, S, Hq, Hkv, D, causal, out_pad,
-                at):
+                at, doc=None):
+        from .attention import attn_forward
+
         N, K = wbuf.shape[0] - pad, wbuf.shape[1] - pad
         x2 = x.reshape(-1, K)
         nat = _lora_native(x2, N, K, splits, r, wbt)
@@ -296,8 +298,8 @@ class _LoRAQKVAttnFn(torch.autograd.Function):
         v = torch.empty_like(k)
         if not ops.gemm8_rope_tail(xa, wbuf[:N, :], cos, sin, B, S, Hq, Hkv, q, k, v, at):
             q, k, v = ops.rope_split(gemm.mm("tn", xa, wbuf[:N, :]), cos, sin, B, S, Hq, Hkv, D)
-        o, lse = ops.attn_fwd(q, k, v, causal, 1.0 / math.sqrt(D), out_pad)
-        ctx.save_for_backward(xa, wbuf, q, k, v, o, lse, cos, sin)
+        o, lse = attn_forward(q, k, v, causal, out_pad, doc)
+        ctx.save_for_backward(xa, wbuf, q, k, v, o, lse, cos, sin, *(doc or ()))
         ctx.lora_a, ctx.lora_b, ctx.wbt, ctx.wxt = a, b, wbt, wxt
         ctx.dims = (N, K, scaling, tuple(splits), r, pad, x.shape, nat, False)
         ctx.causal = causal
@@ -307,21 +309,22 @@ class _LoRAQKVAttnFn(torch.autograd.Function):
     def backward(ctx, do):
         from .attention import backward_dqkv
 
-        xa, wbuf, q, k, v, o, lse, cos, sin = ctx.saved_tensors
+        xa, wbuf, q, k, v, o, lse, cos, sin, *doc = ctx.saved_tensors
         pad = ctx.dims[5]
-        dqkv = backward_dqkv(do, q, k, v, o, lse, cos, sin, ctx.causal, pad)  # left part of [T, N + pad]
+        dqkv = backward_dqkv(do, q, k, v, o, lse, cos, sin, ctx.causal, pad, doc=tuple(doc) or None)  # left of [T, N + pad]
         del q, k, v, o, lse
         dx, da, db = _lora_aug_backward(ctx, xa, wbuf, dqkv, False, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return (dx, da, db) + (None,) * 17
+        return (dx, da, db) + (None,) * 18
 
 
 def lora_qkv_attention(x: torch.Tensor, lin, cos: torch.Tensor, sin: torch.Tensor, B: int, S: int, Hq: int,
-                       Hkv: int, D: int, at: int, causal: bool = True, out_pad: int = 0) -> torch.Tensor:
+                       Hkv: int, D: int, at: int, causal: bool = True, out_pad: int = 0, doc=None) -> torch.Tensor:
     """attention(rope(split(lora_qkv(x)))) -> [B*S, Hq*D] for the LoRA FusedLinear ``lin`` (callers take
-    ``at`` from ``lora_qkv_attention_at``)."""
+    ``at`` from ``lora_qkv_attention_at``).  ``doc``: the packed-document tables (``ops.doc_bounds``)."""
     r = lin.lora_a.shape[0] // len(lin.splits)
     return _LoRAQKVAttnFn.apply(x, lin.lora_a, lin.lora_b, lin.wbuf, lin.scaling, tuple(lin.splits), r, lin.pad,
-                                lin.wbt, getattr(lin, "wxt", None), cos, sin, B, S, Hq, Hkv, D, causal, out_pad, at)
+                                lin.wbt, getattr(lin, "wxt", None), cos, sin, B, S, Hq, Hkv, D, causal, out_pad, at,
+                                doc)
 
 
 def transpose2d(t: torch.Tensor, scale: torch.Tensor | None = None) -> torch.Tensor:

@@ -56,9 +56,10 @@ def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.T
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-              scale: float | None = None) -> torch.Tensor:
+              scale: float | None = None, doc_start: torch.Tensor | None = None) -> torch.Tensor:
     """q [B, S, Hq, D], k/v [B, Sk, Hkv, D] -> o [B, S, Hq, D]  (GQA, fp32 math).
-    Causal alignment is bottom-right (query i sees keys <= i + Sk - S)."""
+    Causal alignment is bottom-right (query i sees keys <= i + Sk - S).  ``doc_start`` [B, S] (packed
+    documents, ``ops.doc_bounds``): query i also sees no key before ``doc_start[b, i]``."""
     B, S, Hq, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     rep = Hq // Hkv
@@ -71,6 +72,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
         i = torch.arange(S, device=q.device).view(S, 1)
         j = torch.arange(Sk, device=q.device).view(1, Sk)
         s = s.masked_fill(j > i + (Sk - S), float("-inf"))
+    if doc_start is not None:
+        j = torch.arange(Sk, device=q.device).view(1, 1, 1, Sk)
+        s = s.masked_fill(j < doc_start.view(B, 1, S, 1), float("-inf"))
     p = torch.softmax(s, dim=-1)
     o = torch.matmul(p, vf)
     return o.transpose(1, 2).to(q.dtype)

@@ -433,34 +433,35 @@ class _PreBackward(torch.autograd.Function):
 
 class _CkptLayer(torch.autograd.Function):
     """Activation-checkpointed transformer layer under ZeRO-3: forward keeps only
-    (x, h); backward re-gathers the unit, recomputes and back-propagates."""
+    (x, h) and the micro-batch's document tables, if any; backward re-gathers the unit, recomputes
+    and back-propagates."""
 
     @staticmethod
-    def forward(ctx, trainer, i, x, h):
+    def forward(ctx, trainer, i, x, h, *doc):
         ctx.trainer, ctx.i = trainer, i
-        ctx.save_for_backward(x, h)
+        ctx.save_for_backward(x, h, *doc)
         with torch.no_grad():
-            xo, ho = trainer.model._layer(i, x, h, trainer._B, trainer._S)
+            xo, ho = trainer.model._layer(i, x, h, trainer._B, trainer._S, doc or None)
         ctx.BS = (trainer._B, trainer._S)
         return xo, ho
 
     @staticmethod
     def backward(ctx, dxo, dho):
         tr = ctx.trainer
-        x, h = ctx.saved_tensors
+        x, h, *doc = ctx.saved_tensors
         uid = tr._units_by_layer[ctx.i].uid
         tr._pre_backward(uid)
         xd = x.detach().requires_grad_(True)
         hd = h.detach().requires_grad_(True)
         with torch.enable_grad():
-            xo, ho = tr.model._layer(ctx.i, xd, hd, *ctx.BS)
+            xo, ho = tr.model._layer(ctx.i, xd, hd, *ctx.BS, tuple(doc) or None)
         outs, grads = [], []
         for o, g in ((xo, dxo), (ho, dho)):
             if g is not None and o.requires_grad:
                 outs.append(o)
                 grads.append(g)
         torch.autograd.backward(outs, grads)
-        return None, None, xd.grad, hd.grad
+        return (None, None, xd.grad, hd.grad) + (None,) * len(doc)
 
 
 class Zero3Trainer:
@@ -709,6 +710,7 @@ class Zero3Trainer:
         cfg = m.cfg
         B, S = ids.shape
         self._B, self._S = B, S
+        doc = m.document_tables(ids)  # packed documents (Llama.set_document_mask), this micro-batch's
         self._wait_update(self.units[0])  # every layer's RMSNorm reads the replicated unit
         for u in self.units:
             u.seen.clear()
@@ -725,9 +727,9 @@ class Zero3Trainer:
                 nxt = self._units_by_layer.get(i + 1, self._head)
                 self._use(u, nxt)
                 if ckpt_layer(self.act_ckpt, i):
-                    x, h = _CkptLayer.apply(self, i, x, h)
+                    x, h = _CkptLayer.apply(self, i, x, h, *(doc or ()))
                 else:
-                    x, h = m._layer(i, x, h, B, S)
+                    x, h = m._layer(i, x, h, B, S, doc)
                     x, h = _PreBackward.apply(self, u.uid, x, h)
                 self._done(u)
             self._use(self._head)

@@ -144,7 +144,10 @@ def main(argv=None):
         tok = get_tokenizer(mcfg.vocab_size, tokenizer_path_for(run.model, run.tokenizer or None), mcfg.bos_id,
                             mcfg.eos_id)
         texts, _ = load_text_dataset(run.dataset, run.split, run.n_rows, run.seed)
-        tokens = pack_texts(texts, tok, getattr(tok, "eos_id", mcfg.eos_id))
+        eos_id = getattr(tok, "eos_id", mcfg.eos_id)
+        tokens = pack_texts(texts, tok, eos_id)
+        if run.doc_mask:  # attention stays inside a packed document (the EOS pack_texts joins them with)
+            trainer.model.set_document_mask(eos_id)
         loader = TokenLoader(tokens, run.seq_len, run.micro_batch, data_rank, data_world, run.seed, env.device)
         steps_per_epoch = max(1, loader.batches_per_epoch // run.grad_accum)
         total = run.steps or run.epochs * steps_per_epoch
