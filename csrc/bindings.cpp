@@ -538,6 +538,63 @@ void adamw_step(const c10::optional<at::Tensor>& master, at::Tensor grad, at::Te
                  (float)bc2, st, (float)scale_f, zero_grad ? 1 : 0, cur_stream()));
 }
 
+// AdamW over fp8 moments (mxllm/ops/optim.py QuantMoment): codes uint8 [n], block exponents int8 [n / 64]
+void adamw8_step(const c10::optional<at::Tensor>& master, at::Tensor grad, at::Tensor m_codes, at::Tensor m_exps,
+                 at::Tensor s_codes, at::Tensor s_exps, const c10::optional<at::Tensor>& lowp,
+                 const c10::optional<at::Tensor>& lo, double lr, double b1, double b2, double eps, double wd,
+                 double bc1, double bc2, const c10::optional<at::Tensor>& scale_t, double scale_f, bool zero_grad,
+                 int64_t key, int64_t base) {
+  MX_CHECK(master.has_value() != lo.has_value(), "give either the fp32 master or the split low half");
+  const int64_t n = m_codes.numel();
+  MX_CHECK(n % 64 == 0, "adamw8: n must be a multiple of the 64-element block");
+  MX_CHECK(base >= 0 && base % 64 == 0, "adamw8: the slice must begin on a block boundary of the flat buffer");
+  const auto dev = m_codes.device();
+  auto aligned = [&](const at::Tensor& t) {  // 16-byte vector access, and one device for every operand
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && t.device() == dev;
+  };
+  for (const at::Tensor* c : {&m_codes, &s_codes})
+    MX_CHECK(c->is_cuda() && c->is_contiguous() && c->scalar_type() == at::kByte && c->numel() == n && aligned(*c),
+             "adamw8: codes must be contiguous 16-byte-aligned uint8 GPU tensors of one size");
+  for (const at::Tensor* e : {&m_exps, &s_exps})
+    MX_CHECK(e->is_cuda() && e->is_contiguous() && e->scalar_type() == at::kChar && e->numel() == n / 64 &&
+                 e->device() == dev,
+             "adamw8: exponents must be contiguous int8 GPU tensors of n / 64 elements on the codes' device");
+  MX_CHECK(grad.is_cuda() && grad.is_contiguous() && grad.numel() == n && aligned(grad),
+           "adamw8: grad must be a contiguous 16-byte-aligned GPU tensor of the moments' size");
+  MX_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16, "grad f32/bf16");
+  float* mp = nullptr;
+  if (master.has_value()) {
+    check_f32(*master, "master");
+    MX_CHECK(master->numel() == n && aligned(*master), "adamw8: master size / alignment");
+    mp = master->data_ptr<float>();
+  }
+  DevGuard g(m_codes.device());
+  uint16_t* lp = nullptr;
+  if (lowp.has_value()) {
+    check_bf16(*lowp, "lowp");
+    MX_CHECK(lowp->numel() == n && aligned(*lowp), "adamw8: lowp size / alignment");
+    lp = reinterpret_cast<uint16_t*>(lowp->data_ptr());
+  }
+  int16_t* lop = nullptr;
+  if (lo.has_value()) {
+    MX_CHECK(lo->is_cuda() && lo->is_contiguous() && lo->scalar_type() == at::kShort && lo->numel() == n &&
+                 aligned(*lo),
+             "lo must be a contiguous 16-byte-aligned int16 GPU tensor of the master's size");
+    MX_CHECK(lp != nullptr, "split master needs lowp (the high half)");
+    lop = lo->data_ptr<int16_t>();
+  }
+  const float* st = nullptr;
+  if (scale_t.has_value()) {
+    check_f32(*scale_t, "scale_t");
+    MX_CHECK(scale_t->numel() >= 1 && scale_t->device() == dev, "adamw8: scale_t needs one element on the device");
+    st = scale_t->data_ptr<float>();
+  }
+  MX_OK(mx_adamw8(mp, grad.data_ptr(), grad.scalar_type() == at::kBFloat16 ? 1 : 0, m_codes.data_ptr<uint8_t>(),
+                  m_exps.data_ptr<int8_t>(), s_codes.data_ptr<uint8_t>(), s_exps.data_ptr<int8_t>(), lp, lop, n,
+                  (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)bc1, (float)bc2, st, (float)scale_f,
+                  zero_grad ? 1 : 0, (uint32_t)key, base, cur_stream()));
+}
+
 // fp32 <-> split master halves (hi bf16 = bits rounded half-up, lo int16 = remainder)
 void split_master(const at::Tensor& x, at::Tensor hi, at::Tensor lo) {
   check_f32(x, "x");
@@ -1951,6 +2008,7 @@ TORCH_LIBRARY(mxllm, m) {
   m.def("swiglu_bwd(Tensor dm, Tensor gu, int out_pad=0) -> Tensor");
   m.def("swiglu_bwd_m(Tensor dm, Tensor gu) -> Tensor[]");
   m.def("adamw_step(Tensor(a!)? master, Tensor(e!) grad, Tensor(b!) m, Tensor(c!) v, Tensor(d!)? lowp, Tensor(f!)? lo, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, Tensor? scale_t, float scale_f, bool zero_grad=False) -> ()");
+  m.def("adamw8_step(Tensor(a!)? master, Tensor(e!) grad, Tensor(b!) m_codes, Tensor(c!) m_exps, Tensor(g!) s_codes, Tensor(h!) s_exps, Tensor(d!)? lowp, Tensor(f!)? lo, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, Tensor? scale_t, float scale_f, bool zero_grad, int key, int base) -> ()");
   m.def("split_master(Tensor x, Tensor(a!) hi, Tensor(b!) lo) -> ()");
   m.def("join_master(Tensor hi, Tensor lo, Tensor(a!) out) -> ()");
   m.def("embedding_fwd(Tensor ids, Tensor w) -> Tensor");
@@ -2025,6 +2083,7 @@ TORCH_LIBRARY_IMPL(mxllm, CUDA, m) {
   m.impl("swiglu_bwd", &swiglu_bwd);
   m.impl("swiglu_bwd_m", &swiglu_bwd_m);
   m.impl("adamw_step", &adamw_step);
+  m.impl("adamw8_step", &adamw8_step);
   m.impl("split_master", &split_master);
   m.impl("join_master", &join_master);
   m.impl("embedding_fwd", &embedding_fwd);

@@ -71,6 +71,9 @@ int mx_swiglu_bwd(const uint16_t* dm, const uint16_t* gu, uint16_t* dgu, int64_t
 int mx_adamw(float* p, void* g, int grad_bf16, float* m, float* v, uint16_t* lowp, int16_t* lo, int64_t n,
              float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, const float* scale_t,
              float scale_f, int zero_grad, hipStream_t stream);
+int mx_adamw8(float* p, void* g, int grad_bf16, uint8_t* mc, int8_t* me, uint8_t* sc, int8_t* se, uint16_t* lowp,
+              int16_t* lo, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2,
+              const float* scale_t, float scale_f, int zero_grad, uint32_t key, int64_t base, hipStream_t stream);
 int mx_split_master(const float* x, uint16_t* hi, int16_t* lo, int64_t n, hipStream_t stream);
 int mx_join_master(const uint16_t* hi, const int16_t* lo, float* x, int64_t n, hipStream_t stream);
 int mx_embedding_fwd(const int64_t* ids, const uint16_t* w, uint16_t* out, int64_t T, int H, int64_t V,

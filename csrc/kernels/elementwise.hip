@@ -151,6 +151,140 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, void*
   }
 }
 
+// ---- AdamW with fp8 moments (mxllm/ops/reference.py adamw8_ states the format and the rounding rule)
+// m and s = sqrt(v) live as OCP e4m3 codes with one int8 power-of-two exponent per block of 64 elements:
+// 2 + 1/32 B/param of state instead of 8.  A lane owns 4 consecutive elements as in adamw_kernel, so the 16
+// lanes of one DPP row own one block: the block's amax is an all-reduce over the row by row rotations (no LDS,
+// no barrier; n % 64 == 0, so a row is wholly inside or outside the loop) and the 4 new values per moment stay
+// in registers until the exponent is known.  p is updated from the fp32 m_new / v_new: adamw_kernel's
+// arithmetic on the decoded old state.
+constexpr int kQ8MinExp = -100;
+
+__device__ __forceinline__ uint32_t q8_fmix(uint32_t h) {  // murmur3's 32-bit finalizer
+  h = (h ^ (h >> 16)) * 0x85EBCA6Bu;
+  h = (h ^ (h >> 13)) * 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+__device__ __forceinline__ float q8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// max over the 16 lanes of the row, in every lane (row_ror 8, 4, 2, 1)
+__device__ __forceinline__ uint32_t q8_row_max(uint32_t a) {
+  a = max(a, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0x128, 0xF, 0xF, false));
+  a = max(a, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0x124, 0xF, 0xF, false));
+  a = max(a, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0x122, 0xF, 0xF, false));
+  a = max(a, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0x121, 0xF, 0xF, false));
+  return a;
+}
+// smallest e with amax / 2^e <= 448 from the bits of a non-negative fp32 amax (kv8_exp's rule)
+__device__ __forceinline__ int q8_exp(uint32_t amax_bits) {
+  if (amax_bits == 0) return 0;
+  return max((int)(amax_bits >> 23) - 135 + ((amax_bits & 0x7FFFFFu) > 0x600000u ? 1 : 0), kQ8MinExp);
+}
+__device__ __forceinline__ f32x4 q8_decode4(uint32_t codes, int e) {
+  const float sc = q8_pow2(e);
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes, true);
+  return f32x4{a[0] * sc, a[1] * sc, b[0] * sc, b[1] * sc};
+}
+// one value times inv = 2^-e -> e4m3 code, stochastically rounded with the 20 random bits r: below the cut of
+// a normal e4m3 number lie 20 fp32 mantissa bits, so adding r to the bit pattern and truncating rounds up with
+// probability (x - lo) / (hi - lo), the carry walking into the exponent by itself; under 2^-6 the grid is the
+// fixed 2^-9 of the subnormals and the same add is done on x 2^29 as an integer
+__device__ __forceinline__ uint32_t q8_round(float x, float inv, uint32_t r) {
+  const uint32_t b = __float_as_uint(x * inv), ab = b & 0x7FFFFFFFu;
+  uint32_t mag;
+  if (ab >= 0x3C800000u)
+    mag = ((ab + r) >> 20) - 960u;
+  else
+    mag = ((uint32_t)(__uint_as_float(ab) * 536870912.f) + r) >> 20;
+  return min(mag, 126u) | ((b >> 24) & 0x80u);
+}
+
+template <bool GRAD_BF16, bool LOWP, bool ZERO, bool SPLIT>
+__global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, void* __restrict__ gv,
+                                                     uint8_t* __restrict__ mc, int8_t* __restrict__ me,
+                                                     uint8_t* __restrict__ sc, int8_t* __restrict__ se,
+                                                     uint16_t* __restrict__ lowp, int16_t* __restrict__ lo,
+                                                     int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                                     float inv_bc1, float inv_bc2, const float* __restrict__ scale_t,
+                                                     float scale_f, uint32_t key, int64_t base) {
+  const float gs = scale_f * (scale_t ? scale_t[0] : 1.f);
+  const float decay = 1.f - lr * wd;
+  const float step = lr * inv_bc1;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 256 * 4) {
+    const int64_t blk = i >> 6;
+    f32x4 g;
+    if constexpr (GRAD_BF16) {
+      u16x4 gb = *reinterpret_cast<const u16x4*>(reinterpret_cast<const uint16_t*>(gv) + i);
+      g = f32x4{bf2f(gb[0]), bf2f(gb[1]), bf2f(gb[2]), bf2f(gb[3])};
+      if constexpr (ZERO) *reinterpret_cast<u16x4*>(reinterpret_cast<uint16_t*>(gv) + i) = u16x4{0, 0, 0, 0};
+    } else {
+      g = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(gv) + i);
+      if constexpr (ZERO) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(gv) + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    f32x4 pp;
+    u16x4 hh;
+    s16x4 ll;
+    if constexpr (SPLIT) {
+      hh = *reinterpret_cast<const u16x4*>(lowp + i);
+      ll = *reinterpret_cast<const s16x4*>(lo + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) pp[j] = split_join(hh[j], ll[j]);
+    } else {
+      pp = *reinterpret_cast<f32x4*>(p + i);
+    }
+    f32x4 mm = q8_decode4(*reinterpret_cast<const uint32_t*>(mc + i), (int)me[blk]);
+    f32x4 ss = q8_decode4(*reinterpret_cast<const uint32_t*>(sc + i), (int)se[blk]);
+    f32x4 vv;
+    u16x4 lw;
+    uint32_t am = 0, as = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gj = g[j] * gs;
+      mm[j] = b1 * mm[j] + (1.f - b1) * gj;
+      vv[j] = b2 * (ss[j] * ss[j]) + (1.f - b2) * gj * gj;
+      const float den = sqrtf(vv[j] * inv_bc2) + eps;
+      pp[j] = pp[j] * decay - step * mm[j] / den;
+      ss[j] = sqrtf(vv[j]);
+      am = max(am, __float_as_uint(mm[j]) & 0x7FFFFFFFu);
+      as = max(as, __float_as_uint(ss[j]));
+      if constexpr (SPLIT) {
+        uint16_t h;
+        int16_t l;
+        split_make(pp[j], h, l);
+        hh[j] = h;
+        ll[j] = l;
+      } else if constexpr (LOWP) {
+        lw[j] = f2bf(pp[j]);
+      }
+    }
+    if constexpr (SPLIT) {
+      *reinterpret_cast<u16x4*>(lowp + i) = hh;
+      *reinterpret_cast<s16x4*>(lo + i) = ll;
+    } else {
+      *reinterpret_cast<f32x4*>(p + i) = pp;
+      if constexpr (LOWP) *reinterpret_cast<u16x4*>(lowp + i) = lw;
+    }
+    const int em = q8_exp(q8_row_max(am)), es = q8_exp(q8_row_max(as));
+    const float im = q8_pow2(-em), is = q8_pow2(-es);
+    uint32_t cm = 0, cs = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      // counter hash of (seed, step: key; moment; global element index)
+      const uint64_t idx = (uint64_t)(base + i + j);
+      const uint32_t a = q8_fmix((uint32_t)idx ^ key) + (uint32_t)(idx >> 32) * 0x9E3779B1u;
+      cm |= q8_round(mm[j], im, q8_fmix(a + 0x3C6EF372u) >> 12) << (8 * j);
+      uint32_t c = q8_round(ss[j], is, q8_fmix(a + 0xDAA66D2Bu) >> 12);
+      if (c == 0 && vv[j] > 0.f) c = 1;  // a positive sqrt(v) is never stored as a zero denominator
+      cs |= c << (8 * j);
+    }
+    *reinterpret_cast<uint32_t*>(mc + i) = cm;
+    *reinterpret_cast<uint32_t*>(sc + i) = cs;
+    if ((threadIdx.x & 15) == 0) {
+      me[blk] = (int8_t)em;
+      se[blk] = (int8_t)es;
+    }
+  }
+}
+
 // fp32 master <-> (hi, lo) halves, element-wise (checkpoint load/save, init)
 __global__ void __launch_bounds__(256) split_master_kernel(const float* __restrict__ x, uint16_t* __restrict__ hi,
                                                            int16_t* __restrict__ lo, int64_t n) {
@@ -377,6 +511,35 @@ extern "C" int mx_adamw(float* p, void* g, int grad_bf16, float* m, float* v, ui
   }
 #undef ADAM_Z
 #undef ADAM_LAUNCH
+  return (int)hipGetLastError();
+}
+
+// AdamW over fp8 moments: mc / sc e4m3 codes [n], me / se int8 block exponents [n / 64]; key = the hash of
+// (seed, step), base = the global flat index of element 0 (both only feed the rounding's random bits)
+extern "C" int mx_adamw8(float* p, void* g, int grad_bf16, uint8_t* mc, int8_t* me, uint8_t* sc, int8_t* se,
+                         uint16_t* lowp, int16_t* lo, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                         float bc1, float bc2, const float* scale_t, float scale_f, int zero_grad, uint32_t key,
+                         int64_t base, hipStream_t stream) {
+  if (n % 64 || base < 0) return -1;
+  if (lo && !lowp) return -1;
+  if (n == 0) return 0;
+  int grid = grid_for(n / 4);
+  if (grid > adamw_grid_cap()) grid = adamw_grid_cap();
+  const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
+#define ADAM8_LAUNCH(GB, LP, Z, SP)                                                                               \
+  adamw8_kernel<GB, LP, Z, SP><<<grid, 256, 0, stream>>>(p, g, mc, me, sc, se, lowp, lo, n, lr, b1, b2, eps, wd, \
+                                                         ib1, ib2, scale_t, scale_f, key, base)
+#define ADAM8_Z(GB, LP, SP) \
+  do { if (zero_grad) ADAM8_LAUNCH(GB, LP, true, SP); else ADAM8_LAUNCH(GB, LP, false, SP); } while (0)
+  if (lo) {
+    if (grad_bf16) ADAM8_Z(true, true, true); else ADAM8_Z(false, true, true);
+  } else if (grad_bf16) {
+    if (lowp) ADAM8_Z(true, true, false); else ADAM8_Z(true, false, false);
+  } else {
+    if (lowp) ADAM8_Z(false, true, false); else ADAM8_Z(false, false, false);
+  }
+#undef ADAM8_Z
+#undef ADAM8_LAUNCH
   return (int)hipGetLastError();
 }
 

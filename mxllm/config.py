@@ -71,6 +71,7 @@ class RunConfig:
     micro_batch: int = 4
     grad_accum: int = 1
     bucket_mb: float = 128.0
+    optim_state: str = "fp32"  # fp32 | fp8 (AdamW moments as block-scaled e4m3: mxllm.ops.QuantMoment)
     activation_checkpointing: bool = False
     ckpt_layers: int = -1  # with activation_checkpointing: -1 = every layer, N = only the first N (selective)
     ckpt_dir: str = ""

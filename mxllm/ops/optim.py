@@ -4,7 +4,8 @@ mxllm keeps every trainable parameter as a view into ONE flat fp32 master
 buffer (and, for full fine-tuning, one flat bf16 compute buffer); gradients
 land in one flat buffer too.  The optimizer step is therefore a single
 vectorised HIP kernel launch per weight-decay group, streaming
-(master, m, v, grad[, bf16 copy]) once: 16-28 B/param, HBM-bound.
+(master, m, v, grad[, bf16 copy]) once: 16-28 B/param, HBM-bound.  With the
+moments in fp8 (:class:`QuantMoment`, ``adamw8_kernel``): 14-16 B/param.
 """
 from __future__ import annotations
 
@@ -99,17 +100,133 @@ class SplitMaster:
         return self
 
 
-def adamw_step_(master, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
-                lowp: torch.Tensor | None, *, lr: float, beta1: float, beta2: float, eps: float,
-                weight_decay: float, step: int, grad_scale=1.0, zero_grad: bool = False) -> None:
+class QuantMoment:
+    """One AdamW moment of a flat buffer in 8 bits (2 + 1/32 B/param for both moments instead of 8).
+
+    Format (``mxllm/ops/reference.py`` ``q8_*`` define it, ``adamw8_kernel`` implements it): a block is 64
+    consecutive elements of the FLAT buffer; ``codes`` uint8 [n] are OCP e4m3 codes and ``exps`` int8 [n / 64]
+    one power-of-two exponent per block, value = e4m3(code) 2^e, e the smallest with amax / 2^e <= 448 (at least
+    -100; 0 for an all-zero block).  ``sqrt=True`` (the second moment): the stored quantity is s = sqrt(v) --
+    e4m3 spans 2^18 inside a block, which as v would leave the denominators a range of 500 -- and a positive s
+    is stored no smaller than the smallest subnormal, so an update never divides by a flushed zero.  The
+    optimizer step rounds STOCHASTICALLY (to-nearest would return sqrt(v) to its old code every step: a 0.1 %
+    change against a 6 % spacing) with bits hashed from (``seed``, step, moment, global element index
+    ``base`` + i), so the result does not depend on the grid, the chunking or the rank that holds the element.
+
+    Where the trainers need it, it stands in for a 1-D fp32 tensor: slicing on block boundaries (views; ``base``
+    follows), ``numel``, ``zero_``, ``float()`` (the decoded fp32 moment: v = s^2 when ``sqrt``) and ``copy_``
+    (from a QuantMoment: codes and exponents as they are; from fp32: round to NEAREST, so a loaded checkpoint is
+    deterministic).  Accuracy on real checkpoints has not been measured."""
+
+    BLOCK = ref.Q8_BLOCK
+    dtype = torch.float32
+
+    def __init__(self, codes: torch.Tensor, exps: torch.Tensor | None = None, *, sqrt: bool = False, seed: int = 0,
+                 base: int = 0):
+        if codes.dtype != torch.uint8 or codes.dim() != 1 or codes.numel() % self.BLOCK or base % self.BLOCK:
+            raise ValueError("QuantMoment: uint8 codes of whole 64-element blocks starting on a block boundary")
+        self.codes = codes
+        self.exps = exps if exps is not None else torch.zeros(codes.numel() // self.BLOCK, dtype=torch.int8,
+                                                              device=codes.device)
+        if self.exps.dtype != torch.int8 or self.exps.numel() != codes.numel() // self.BLOCK:
+            raise ValueError("QuantMoment: one int8 exponent per 64 codes")
+        self.sqrt, self.seed, self.base = sqrt, int(seed), int(base)
+
+    @classmethod
+    def zeros(cls, n: int, device=None, **kw):
+        return cls(torch.zeros(n, dtype=torch.uint8, device=device), **kw)
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    @property
+    def is_cuda(self):
+        return self.codes.is_cuda
+
+    def numel(self) -> int:
+        return self.codes.numel()
+
+    def __getitem__(self, sl):
+        if not isinstance(sl, slice) or sl.step not in (None, 1):
+            raise ValueError("QuantMoment: contiguous slices only")
+        lo, hi, _ = sl.indices(self.numel())
+        if lo % self.BLOCK or hi % self.BLOCK:
+            raise ValueError(f"QuantMoment: slice [{lo}, {hi}) does not lie on 64-element block boundaries")
+        return QuantMoment(self.codes[lo:hi], self.exps[lo // self.BLOCK:hi // self.BLOCK], sqrt=self.sqrt,
+                           seed=self.seed, base=self.base + lo)
+
+    def at(self, base: int):
+        """The same storage as the elements [base, base + n) of the flat buffer (a rank's compact shard)."""
+        return QuantMoment(self.codes, self.exps, sqrt=self.sqrt, seed=self.seed, base=base)
+
+    def float(self) -> torch.Tensor:
+        x = ref.q8_decode(self.codes, self.exps)
+        return x * x if self.sqrt else x
+
+    def zero_(self):
+        self.codes.zero_()
+        self.exps.zero_()
+        return self
+
+    def copy_(self, src):
+        if isinstance(src, QuantMoment):
+            if src.sqrt != self.sqrt:
+                raise ValueError("QuantMoment.copy_: one holds sqrt(v), the other does not")
+            self.codes.copy_(src.codes)
+            self.exps.copy_(src.exps)
+            return self
+        x = src.to(device=self.codes.device, dtype=torch.float32).reshape(self.codes.shape)
+        ref.q8_encode_(self.codes, self.exps, x.sqrt() if self.sqrt else x, floor_min=(x > 0) if self.sqrt else None)
+        return self
+
+
+def copy_moment_(dst, src) -> None:
+    """``dst.copy_(src)`` for any pairing of fp32 and fp8 optimizer state (checkpoints written with the other
+    setting): fp8 -> fp32 decodes, fp32 -> fp8 rounds to nearest, fp8 -> fp8 copies codes and exponents."""
+    dst.copy_(src.float() if isinstance(src, QuantMoment) and not isinstance(dst, QuantMoment) else src)
+
+
+def adamw_step_(master, grad: torch.Tensor, m, v, lowp: torch.Tensor | None, *, lr: float, beta1: float,
+                beta2: float, eps: float, weight_decay: float, step: int, grad_scale=1.0,
+                zero_grad: bool = False) -> None:
     """In-place AdamW on flat 1-D tensors (``grad`` fp32 or bf16).
 
     ``master``: an fp32 tensor (``lowp``: optional bf16 copy to refresh) or a
     :class:`SplitMaster` (its ``hi`` half IS the bf16 copy; ``lowp`` ignored).
+    ``m`` / ``v``: fp32 tensors, or two :class:`QuantMoment` (``v`` with ``sqrt=True``): fp8 state.
     ``grad_scale`` is a float or a 1-element f32 device tensor (e.g. the
     grad-clip coefficient x 1/world computed on device: no host sync).
     ``zero_grad``: clear ``grad`` in the same pass (GPU: fused into the kernel)."""
     split = isinstance(master, SplitMaster)
+    quant = isinstance(m, QuantMoment)
+    if quant != isinstance(v, QuantMoment) or (quant and (m.sqrt or not v.sqrt or m.numel() != v.numel()
+                                                          or m.base != v.base or m.seed != v.seed)):
+        raise ValueError("adamw_step_: fp8 state needs m = QuantMoment and v = QuantMoment(sqrt=True) of one range")
+    if quant and use_native(m.codes):
+        if isinstance(grad_scale, torch.Tensor):
+            st, sf = grad_scale.reshape(1).float().contiguous(), 1.0
+        else:
+            st, sf = None, float(grad_scale)
+        native().adamw8_step(None if split else master, grad, m.codes, m.exps, v.codes, v.exps,
+                             master.hi if split else lowp, master.lo if split else None, lr, beta1, beta2, eps,
+                             weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, st, sf, bool(zero_grad),
+                             ref.q8_key(m.seed, step), m.base)
+        return
+    if quant:
+        p = master.float() if split else master
+        ref.adamw8_(p, grad, m.codes, m.exps, v.codes, v.exps, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                    weight_decay=weight_decay, step=step, grad_scale=grad_scale, p_lowp=None if split else lowp,
+                    seed=m.seed, base=m.base)
+        if split:
+            master.copy_(p)
+        if zero_grad:
+            grad.zero_()
+        return
     if use_native(m):
         bc1 = 1.0 - beta1 ** step
         bc2 = 1.0 - beta2 ** step

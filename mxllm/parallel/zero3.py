@@ -470,14 +470,15 @@ class Zero3Trainer:
     def __init__(self, cfg, env: DistEnv, optim=None, *, seed: int = 0, activation_checkpointing: bool | int = False,
                  process_group=None, emulate_world: int = 0, max_inflight: int | None = None,
                  init_from: str | None = None, grad_dtype: torch.dtype | None = torch.float32,
-                 rs_group=None):
+                 rs_group=None, optim_state: str | None = None):
         """``grad_dtype``: dtype the unit gradients are formed, reduce-scattered and
         accumulated in — fp32 by default (no bf16 rounding at any ring hop; the dW
         GEMMs write fp32 output), ``torch.bfloat16`` halves the reduce-scatter
         bytes.  ``None`` = fp32."""
         from ..models.llama import Llama
-        from ..train.trainer import OptimConfig
+        from ..train.trainer import OptimConfig, resolve_optim_state
 
+        self.optim_state = resolve_optim_state(optim_state)
         self.env, self.opt = env, optim or OptimConfig()
         self.act_ckpt = activation_checkpointing
         self.pg = process_group
@@ -519,10 +520,21 @@ class Zero3Trainer:
         self.master = (ops.SplitMaster(self.shard_params) if self.split_master
                        else torch.empty(total, dtype=torch.float32, device=dev))
         self.grads = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
+        if self.optim_state == "fp8":
+            # fp8 moments (ops.QuantMoment): every unit shard is a multiple of 64 elements.  The rounding's counter
+            # is the element's index in the unit's content (world-independent: rank r holds [r S, (r + 1) S)) past
+            # the 64-rounded sizes of the units before it, so resharding does not change what a step computes
+            self.m = ops.QuantMoment.zeros(total, dev, seed=seed)
+            self.v = ops.QuantMoment.zeros(total, dev, seed=seed, sqrt=True)
+        else:
+            self.m = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.v = torch.zeros(total, dtype=torch.float32, device=dev)
+        off = q8 = 0
         for u in self.units:
+            # (a unit's padding past its 64-rounded size shares counter values with the next unit's first
+            # elements: harmless, pad elements have zero gradient and state and stay zero whatever the bits)
+            u.q8_base = q8 + (0 if u.replicated else self.rank * u.shard_numel)
+            q8 += (u.numel + 63) // 64 * 64
             u.shard = self.shard_params[off:off + u.shard_numel]
             u.grad_shard = self.grads[off:off + u.shard_numel]
             u.master_view = self.master[off:off + u.shard_numel]
@@ -784,7 +796,10 @@ class Zero3Trainer:
             gscale = scale
         kw = dict(lr=o.lr_at(self.step_num), beta1=o.beta1, beta2=o.beta2, eps=o.eps, weight_decay=o.weight_decay,
                   step=self.step_num, grad_scale=gscale, zero_grad=False)  # every shard is overwritten next step
-        if self._side is None:
+        if self._side is None and self.optim_state == "fp8":
+            for u in self.units:  # one launch per unit: the counter base changes with the unit
+                self._adamw_unit(u, kw)
+        elif self._side is None:
             ops.adamw_step_(self.master, self.grads, self.m, self.v, self.shard_params, **kw)
         else:
             self._launch_overlapped(kw)
@@ -799,12 +814,18 @@ class Zero3Trainer:
         self._hold = kw["grad_scale"]  # read on the side stream: keep it alive until the next step
         with torch.cuda.stream(side):
             for u in self._fwd_order:
-                off = u.grad_shard.storage_offset() - self.grads.storage_offset()
-                sl = slice(off, off + u.shard_numel)
-                ops.adamw_step_(self.master[sl], self.grads[sl], self.m[sl], self.v[sl], self.shard_params[sl], **kw)
+                self._adamw_unit(u, kw)
                 ev = torch.cuda.Event()
                 ev.record(side)
                 self._pending[u.uid] = ev
+
+    def _adamw_unit(self, u, kw):
+        off = u.grad_shard.storage_offset() - self.grads.storage_offset()
+        sl = slice(off, off + u.shard_numel)
+        m, v = self.m[sl], self.v[sl]
+        if self.optim_state == "fp8":
+            m, v = m.at(u.q8_base), v.at(u.q8_base)
+        ops.adamw_step_(self.master[sl], self.grads[sl], m, v, self.shard_params[sl], **kw)
 
     def _refresh_resident(self):
         # the replicated unit IS its shard (updated in place by AdamW): re-point its parameters
@@ -821,8 +842,8 @@ class Zero3Trainer:
 
     def load_state_dict(self, sd):
         self.master.copy_(sd["master"])
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        ops.copy_moment_(self.m, sd["m"])
+        ops.copy_moment_(self.v, sd["v"])
         self.finish_load(int(sd["step"]))
 
     def finish_load(self, step: int):

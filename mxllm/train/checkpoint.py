@@ -4,7 +4,9 @@ Layout ``<dir>/step_<N>/`` (format 2):
   manifest.json                 step, world, parallel kind, flat-buffer slot table
                                 / ZeRO-3 unit table, piece list, loader state
   optim/part_<k>.safetensors    DDP: rank 0's optimizer state (fp32 master, m, v)
-                                in flat-buffer ranges of <= PIECE_ELEMS elements
+                                in flat-buffer ranges of <= PIECE_ELEMS elements;
+                                fp8 moments (``ops.QuantMoment``) as they are:
+                                ``m.codes`` / ``m.exps`` / ``v.codes`` / ``v.exps``
   rank_<r>.safetensors          ZeRO-1: rank r's optimizer shards (compact layout)
   z3/rank_<r>/unit_<u>.safetensors
                                 ZeRO-3: rank r's shard of unit u (master, m, v)
@@ -19,6 +21,8 @@ builds a whole-state dict.  Resharding: a ZeRO-3 checkpoint written at world N
 resumes at world M — every rank reads the byte ranges of its new shard out of
 the old ranks' unit files (``safe_open(...).get_slice``, nothing else is read).
 A DDP checkpoint resumes into a different flat layout by slot name.
+A checkpoint written with fp32 moments loads into fp8 state (rounded to nearest)
+and one written with fp8 moments into fp32 state (decoded).
 Only safetensors/JSON are used: nothing is ever unpickled.
 """
 from __future__ import annotations
@@ -32,6 +36,8 @@ import torch
 import torch.distributed as dist
 from safetensors import safe_open
 from safetensors.torch import load_file, save_file
+
+from ..ops.optim import QuantMoment
 
 log = logging.getLogger("mxllm.ckpt")
 FORMAT = 2
@@ -59,7 +65,10 @@ def _barrier():
 
 def _write(path: str, tensors: dict):
     """Stage ``tensors`` on the host and write one safetensors file."""
-    host = {k: v.detach().contiguous().cpu() for k, v in tensors.items()}
+    flat = {}
+    for k, v in tensors.items():  # fp8 moments: codes and exponents as stored
+        flat.update({k + ".codes": v.codes, k + ".exps": v.exps} if isinstance(v, QuantMoment) else {k: v})
+    host = {k: v.detach().contiguous().cpu() for k, v in flat.items()}
     _STAGED["peak"] = max(_STAGED["peak"], sum(t.numel() * t.element_size() for t in host.values()))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     save_file(host, path)
@@ -114,8 +123,11 @@ def save(ckpt_dir: str, trainer, step: int, extra: dict | None = None, sharded: 
 def _save_flat(d: str, trainer) -> list:
     n = trainer._master.numel()
     pieces = []
-    for k, lo in enumerate(range(0, n, PIECE_ELEMS)):
-        hi = min(n, lo + PIECE_ELEMS)
+    piece = PIECE_ELEMS
+    if isinstance(trainer.m, QuantMoment):  # fp8 moments are cut on their 64-element blocks
+        piece = max(piece // QuantMoment.BLOCK, 1) * QuantMoment.BLOCK
+    for k, lo in enumerate(range(0, n, piece)):
+        hi = min(n, lo + piece)
         _write(os.path.join(d, "optim", f"part_{k:05d}.safetensors"),
                {"master": trainer._master[lo:hi], "m": trainer.m[lo:hi], "v": trainer.v[lo:hi]})
         pieces.append([lo, hi])
@@ -199,6 +211,9 @@ def load(ckpt_dir: str, trainer, step: int | None = None) -> dict | None:
             raise RuntimeError(f"ZeRO-1 checkpoint written with world {man['world_size']}, resuming with {world}")
         _require_same_layout(man.get("layout"), trainer.flat.state_dict(), "ZeRO-1")
         sd = {k: v.to(trainer._master.device) for k, v in load_file(os.path.join(d, f"rank_{rank}.safetensors")).items()}
+        for k in ("m", "v"):
+            if k + ".codes" in sd:
+                sd[k] = QuantMoment(sd.pop(k + ".codes"), sd.pop(k + ".exps"), sqrt=k == "v")
         sd["step"] = man["step"]
         trainer.load_state_dict(sd)
     else:
@@ -206,14 +221,51 @@ def load(ckpt_dir: str, trainer, step: int | None = None) -> dict | None:
         for k, (lo, hi) in enumerate(man["pieces"]):
             with safe_open(os.path.join(d, "optim", f"part_{k:05d}.safetensors"), framework="pt") as f:
                 for key, dst in (("master", trainer._master), ("m", trainer.m), ("v", trainer.v)):
-                    sl = f.get_slice(key)
+                    src = _stored(f, key)
                     for olo, ohi, nlo in segs:
                         a, b = max(olo, lo), min(ohi, hi)
                         if a < b:
-                            dst[nlo + a - olo:nlo + b - olo].copy_(sl[a - lo:b - lo])
+                            _put(dst, nlo + a - olo, src, a - lo, b - lo)
         trainer.finish_load(man["step"])
     log.info("resumed from %s", d)
     return man.get("extra", {})
+
+
+class _StoredMoment:
+    """An fp8 moment in an open safetensors file; a block-aligned slice reads only its codes and exponents."""
+
+    def __init__(self, f, key: str):
+        self.codes, self.exps, self.sqrt = f.get_slice(key + ".codes"), f.get_slice(key + ".exps"), key == "v"
+
+    def __getitem__(self, sl: slice) -> QuantMoment:
+        B = QuantMoment.BLOCK
+        return QuantMoment(self.codes[sl.start:sl.stop], self.exps[sl.start // B:sl.stop // B], sqrt=self.sqrt)
+
+
+def _stored(f, key: str):
+    """Tensor ``key`` of an open safetensors file as a lazy slice (fp8 moments: of codes and exponents)."""
+    return _StoredMoment(f, key) if key + ".codes" in f.keys() else f.get_slice(key)
+
+
+def _put(dst, start: int, src, a: int, b: int) -> None:
+    """dst[start:start + b - a] = src[a:b], in any pairing of fp32 and fp8 state.  fp8 moments move as whole
+    64-element blocks: every range begins on a block (slots, pieces and shards do), and one that ends with its
+    slot or unit is filled up with the zeros that the alignment pad behind it holds."""
+    B = QuantMoment.BLOCK
+    if isinstance(dst, QuantMoment) and (start % B or (isinstance(src, _StoredMoment) and a % B)):
+        raise RuntimeError(f"fp8 optimizer state is loaded in whole {B}-element blocks, but the checkpoint cuts a range "
+                           f"at element {a} -> {start} (written with MXLLM_CKPT_PIECE_ELEMS not a multiple of {B}?)")
+    if isinstance(src, _StoredMoment):
+        if isinstance(dst, QuantMoment):  # the stored bytes
+            n = (b - a + B - 1) // B * B
+            dst[start:start + n].copy_(src[a:a + n])
+            return
+        x = src[a // B * B:(b + B - 1) // B * B].float()[a % B:a % B + b - a]
+    else:
+        x = src[a:b]
+    if isinstance(dst, QuantMoment) and (b - a) % B:
+        x = torch.cat([x.float(), torch.zeros(-(b - a) % B)])
+    dst[start:start + x.numel()].copy_(x)
 
 
 def _norm_slots(layout: dict | None):
@@ -298,8 +350,7 @@ def _load_zero3(d, man, tr, rank, world):
             path = os.path.join(d, "z3", f"rank_{q}", f"unit_{u.uid:04d}.safetensors")
             with safe_open(path, framework="pt") as f:
                 for key, buf in (("master", tr.master), ("m", tr.m), ("v", tr.v)):
-                    src = f.get_slice(key)[lo - q * S_old:hi - q * S_old]
-                    buf[off + lo - a0:off + hi - a0].copy_(src)
+                    _put(buf, off + lo - a0, _stored(f, key), lo - q * S_old, hi - q * S_old)
 
 
 def load_model_weights(model, path: str) -> None:

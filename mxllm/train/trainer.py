@@ -44,6 +44,14 @@ class OptimConfig:
         return self.lr
 
 
+def resolve_optim_state(value: str | None) -> str:
+    """``fp32`` | ``fp8`` from an option, else from ``MXLLM_OPTIM_STATE`` (default fp32)."""
+    value = (value or os.environ.get("MXLLM_OPTIM_STATE", "") or "fp32").lower()
+    if value not in ("fp32", "fp8"):
+        raise ValueError(f"optimizer state {value!r}: fp32 or fp8")
+    return value
+
+
 def _overlap_default() -> bool:
     return os.environ.get("MXLLM_OVERLAP_ADAMW", "1") != "0"
 
@@ -64,7 +72,8 @@ class Trainer:
     def __init__(self, model: torch.nn.Module, env: DistEnv, optim: OptimConfig | None = None, *,
                  bucket_mb: float = 128.0, first_bucket_mb: float = 16.0, broadcast_init: bool = False,
                  shard_optimizer: bool = False, overlap_optimizer: bool | None = None,
-                 grad_dtype: torch.dtype | str | None = None):
+                 grad_dtype: torch.dtype | str | None = None, optim_state: str | None = None,
+                 optim_seed: int = 0):
         """``shard_optimizer``: ZeRO-1 (mxllm/parallel/zero1.py) — gradients are
         reduce-scattered, each rank updates its 1/N slice, parameters are
         all-gathered back.  At world 1 it is plain DDP (nothing to shard).
@@ -76,7 +85,12 @@ class Trainer:
         ``grad_dtype``: dtype of the flat gradient buffer = the dtype gradients are
         ACCUMULATED (micro-batches) and ALL-REDUCED in.  ``torch.float32``: fp32
         accumulation and fp32 ring reduction (the dW GEMMs write fp32 output);
-        default: the parameter dtype (bf16)."""
+        default: the parameter dtype (bf16).
+
+        ``optim_state``: ``"fp32"`` (default) or ``"fp8"`` -- the AdamW moments as block-scaled e4m3 codes
+        (:class:`mxllm.ops.QuantMoment`: 2 + 1/32 B/param instead of 8), stochastically rounded from
+        ``optim_seed``; None = ``MXLLM_OPTIM_STATE``.  Accuracy on real checkpoints has not been measured."""
+        self.optim_state = resolve_optim_state(optim_state)
         self.model = model
         self.env = env
         self.opt = optim or OptimConfig()
@@ -101,8 +115,12 @@ class Trainer:
         if broadcast_init:
             self.ddp.broadcast_params(0)
         self._sync_adapters()
-        self.m = torch.zeros(self._master.numel(), dtype=torch.float32, device=self._master.device)
-        self.v = torch.zeros_like(self.m)
+        if self.optim_state == "fp8":  # (every slot, forward chunk and ZeRO-1 bucket shard begins on a 64-block)
+            self.m = ops.QuantMoment.zeros(self._master.numel(), self._master.device, seed=optim_seed)
+            self.v = ops.QuantMoment.zeros(self._master.numel(), self._master.device, seed=optim_seed, sqrt=True)
+        else:
+            self.m = torch.zeros(self._master.numel(), dtype=torch.float32, device=self._master.device)
+            self.v = torch.zeros_like(self.m)
         self.step_num = 0
         self.last_grad_norm: torch.Tensor | None = None
         # ---- optimizer / next-forward overlap
@@ -462,9 +480,17 @@ class Trainer:
             gscale = scale
         if z is not None:
             lowp = None if z.master is z.pshard else z.pshard
-            ops.adamw_step_(z.master, grads, self.m, self.v, lowp, lr=o.lr_at(self.step_num), beta1=o.beta1,
-                            beta2=o.beta2, eps=o.eps, weight_decay=o.weight_decay, step=self.step_num,
-                            grad_scale=gscale, zero_grad=True)
+            kw = dict(lr=o.lr_at(self.step_num), beta1=o.beta1, beta2=o.beta2, eps=o.eps,
+                      weight_decay=o.weight_decay, step=self.step_num, grad_scale=gscale, zero_grad=True)
+            if self.optim_state == "fp8":
+                # one launch per bucket shard: the rounding's random bits are keyed by the FLAT index of an
+                # element, and the compact shard is contiguous in the flat buffer only inside a bucket
+                for b, (cs, n) in zip(z.buckets, z.cslices):
+                    sl, at = slice(cs, cs + n), b.start + z.rank * n
+                    ops.adamw_step_(z.master[sl], grads[sl], self.m[sl].at(at), self.v[sl].at(at),
+                                    None if lowp is None else lowp[sl], **kw)
+            else:
+                ops.adamw_step_(z.master, grads, self.m, self.v, lowp, **kw)
             z.gather_params()  # async, forward order; the next forward waits per layer
             if getattr(self.model, "sync_adapters_", None) is not None and getattr(self.model, "lora", False):
                 z.wait_params()
@@ -522,8 +548,8 @@ class Trainer:
     def load_state_dict(self, sd: dict):
         self.params_ready()
         self._master.copy_(sd["master"])
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        ops.copy_moment_(self.m, sd["m"])  # (a state dict of the other MXLLM_OPTIM_STATE is converted)
+        ops.copy_moment_(self.v, sd["v"])
         self.finish_load(int(sd["step"]))
 
     def finish_load(self, step: int):

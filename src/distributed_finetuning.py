@@ -70,10 +70,11 @@ def build_trainer(run, env):
         from mxllm.parallel.zero3 import Zero3Trainer
 
         return Zero3Trainer(cfg, env, opt, seed=run.seed, activation_checkpointing=_ckpt_setting(run),
-                            init_from=run.model if is_hf_dir(run.model) else None)
+                            init_from=run.model if is_hf_dir(run.model) else None, optim_state=run.optim_state)
     model = build_model(run.model, device=env.device, lora_r=lora_r, lora_alpha=run.lora_alpha, seed=run.seed,
                         activation_checkpointing=_ckpt_setting(run))
-    return Trainer(model, env, opt, bucket_mb=run.bucket_mb, shard_optimizer=run.parallel == "zero1")
+    return Trainer(model, env, opt, bucket_mb=run.bucket_mb, shard_optimizer=run.parallel == "zero1",
+                   optim_state=run.optim_state, optim_seed=run.seed)
 
 
 def export_hf(run, trainer, rank):
